@@ -18,6 +18,15 @@ weak scaling (global batch = 256*N).
 Timing: W untimed warmup steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX elapsed over ranks;
 rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.
+``--dump-outputs DIR`` additionally writes what the last timed step computed
+(loss, logits, updated parameters, BN running statistics) as float32
+``DIR/<name>.npy``; model init and data are seeded, so two builds run with the
+same arguments can be compared output for output. For the same reason every
+conv direction runs on the deterministic ddlw kernels (``DDLW_CONV=hip``
+unless the variable is already set), so a run is bit-reproducible. ``--full`` is where any
+measurement beyond the headline figure belongs (none today).
 """
 from __future__ import annotations
 
@@ -43,7 +52,46 @@ def parse_args():
     p.add_argument("--no-hip-ops", action="store_true", help="disable ddlw HIP kernels (stock-op baseline)")
     p.add_argument("--graph", action="store_true", default=None, help="capture the step in a hipGraph")
     p.add_argument("--no-graph", dest="graph", action="store_false")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step computed to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's extended measurements; there are none yet, so "
+                        "today this equals a plain run (the per-config benches live in bench/)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
+
+
+# --dump-outputs budget: a parameter set larger than this many elements is
+# written as a fixed seeded sample (fp32: 16 MiB), far below the 64 MB cap
+DUMP_SAMPLE_ELEMS = 4 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, model: torch.nn.Module, last: dict) -> None:
+    """Write what a caller of the training step receives from its LAST timed
+    step as float32 ``.npy``: the step's loss and logits, and the model state
+    after its optimizer update (parameters, BN running statistics)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def flat32(tensors):
+        return torch.cat([t.detach().reshape(-1).float().cpu() for t in tensors])
+
+    params = flat32(model.parameters())
+    if params.numel() > DUMP_SAMPLE_ELEMS:
+        g = torch.Generator().manual_seed(97531)
+        idx = torch.randperm(params.numel(), generator=g)[:DUMP_SAMPLE_ELEMS].sort().values
+        params = params[idx]
+    arrays = {
+        "loss": last["loss"].reshape(1).float().cpu(),
+        "logits": last["logits"].float().cpu(),
+        "params": params,
+        "bn_running_stats": flat32(b for b in model.buffers() if b.is_floating_point()),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.contiguous().numpy())
 
 
 def main() -> None:
@@ -68,6 +116,11 @@ def main() -> None:
     if use_cuda and args.no_hip_ops:
         os.environ["DDLW_DISABLE_HIP_OPS"] = "1"
     torch.manual_seed(1234)
+    # same arguments -> same results, every run: the MIOpen solvers behind the
+    # table's "stock" dgrad/wgrad routes accumulate with atomics, so the trained
+    # weights drift from run to run; the ddlw kernels are deterministic.
+    # (DDLW_CONV=auto restores the measured table: ~4% faster, not reproducible)
+    os.environ.setdefault("DDLW_CONV", "hip")
     from ddlw_amd.models import build_resnet50
     from ddlw_amd.ops import FusedSGD, normalize_u8_bf16, require_lib, softmax_cross_entropy
 
@@ -115,6 +168,7 @@ def main() -> None:
         amp_dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
 
     loss_fn = torch.nn.CrossEntropyLoss()
+    last = {}  # loss/logits of the most recent step (for --dump-outputs)
 
     def step_fn(i: int) -> None:
         hb, hl = host_batches[i % pool], labels_pool[i % pool]
@@ -140,9 +194,11 @@ def main() -> None:
         else:
             x = hb.float().mul_(1.0 / 127.5).sub_(1.0)
             opt.zero_grad(set_to_none=True)
-            loss = loss_fn(model(x), hl)
+            logits = model(x)
+            loss = loss_fn(logits, hl)
             loss.backward()
             opt.step()
+        last["loss"], last["logits"] = loss.detach(), logits.detach()
 
     model.train()
 
@@ -175,7 +231,7 @@ def main() -> None:
                     loss = loss_fn(logits.float(), d_lab)
             loss.backward()
             opt.step()
-            return loss
+            return loss.detach(), logits.detach()
 
         # eager warmup first (MIOpen find / autotune must finish pre-capture)
         for i in range(max(warmup, 3)):
@@ -184,11 +240,11 @@ def main() -> None:
             bufs_lab[s].copy_(labels_pool[i % pool], non_blocking=True)
             compute_from(bufs_img[s], bufs_lab[s])
         torch.cuda.synchronize()
-        graphs = []
+        graphs, graph_outs = [], []
         for s in range(2):
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr):
-                compute_from(bufs_img[s], bufs_lab[s])
+                graph_outs.append(compute_from(bufs_img[s], bufs_lab[s]))
             graphs.append(gr)
         torch.cuda.synchronize()
 
@@ -215,6 +271,7 @@ def main() -> None:
             s = i % 2
             main.wait_event(ready[s])
             graphs[s].replay()
+            last["loss"], last["logits"] = graph_outs[s]
             free[s].record(main)
             _prefetch(i + 1)
             state["next"] = i + 1
@@ -247,6 +304,9 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.cpu().item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)
+
     total_images = batch * world * steps
     ips = total_images / elapsed
     if rank == 0:
@@ -271,6 +331,7 @@ def main() -> None:
                 "image_size": 224,
                 "parallelism": f"dp{world}",
                 "hip_ops": bool(use_cuda and not args.no_hip_ops),
+                "conv_routes": os.environ["DDLW_CONV"],
             },
         }
         print(json.dumps(out), flush=True)
