@@ -10,11 +10,25 @@ layer, so its BatchNorms must run with *moving statistics* even in training
 mode — here the base is put in eval() and its params have
 ``requires_grad=False``; ``FrozenBase.train()`` keeps it in eval mode.
 
+Fine-tuning (``fine_tune_at=k``): ``features[k:]`` becomes trainable while
+``features[:k]`` stays frozen as above — the second phase of transfer
+learning (train the head, then unfreeze the top of the base at a low
+learning rate). The trainable suffix follows ``train()``/``eval()`` like any
+module, so its BatchNorms use *batch* statistics in training. That is what
+the reference's per-layer ``trainable`` flags give; it is NOT the Keras
+fine-tuning recipe that keeps calling the base with ``training=False``.
+
+Activations: every BN + ReLU6 pair is one fused ``BatchNormAct2d(act=
+"relu6")``; an ``nn.Identity`` keeps the old ReLU6 slot so ``state_dict``
+keys and ``features`` indices are unchanged and saved models still load.
+
 No pretrained weights exist in this offline environment, so the base is
 randomly initialised (documented deviation; the benchmark configs use
 random-init weights anyway, BASELINE.json).
 """
 from __future__ import annotations
+
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -33,13 +47,13 @@ class InvertedResidual(nn.Module):
         if expand != 1:
             layers += [
                 Conv2d(in_ch, hidden, 1, bias=False),
-                BatchNormAct2d(hidden),
-                nn.ReLU6(inplace=True),
+                BatchNormAct2d(hidden, act="relu6"),
+                nn.Identity(),  # old ReLU6 slot (fused into the BN above)
             ]
         layers += [
             Conv2d(hidden, hidden, 3, stride=stride, padding=1, groups=hidden, bias=False),
-            BatchNormAct2d(hidden),
-            nn.ReLU6(inplace=True),
+            BatchNormAct2d(hidden, act="relu6"),
+            nn.Identity(),
             Conv2d(hidden, out_ch, 1, bias=False),
             BatchNormAct2d(out_ch),
         ]
@@ -68,8 +82,8 @@ class MobileNetV2(nn.Module):
         super().__init__()
         blocks = [
             Conv2d(channels, 32, 3, stride=2, padding=1, bias=False),
-            BatchNormAct2d(32),
-            nn.ReLU6(inplace=True),
+            BatchNormAct2d(32, act="relu6"),
+            nn.Identity(),
         ]
         in_ch = 32
         for t, c, n, s in _V2_CFG:
@@ -78,8 +92,8 @@ class MobileNetV2(nn.Module):
                 in_ch = c
         blocks += [
             Conv2d(in_ch, 1280, 1, bias=False),
-            BatchNormAct2d(1280),
-            nn.ReLU6(inplace=True),
+            BatchNormAct2d(1280, act="relu6"),
+            nn.Identity(),
         ]
         self.features = nn.Sequential(*blocks)
         for m in self.modules():
@@ -95,38 +109,100 @@ class MobileNetV2(nn.Module):
 
 class FrozenBase(nn.Module):
     """Wraps a base so it stays in eval mode (frozen BN -> moving stats,
-    reference ``.../02_model_training_single_node.py:167-169``)."""
+    reference ``.../02_model_training_single_node.py:167-169``).
 
-    def __init__(self, base: nn.Module):
+    ``fine_tune_at=k`` unfreezes ``base.features[k:]``: those children get
+    ``requires_grad=True`` and follow ``train()``/``eval()``;
+    ``base.features[:k]`` keeps ``requires_grad=False``, stays in ``eval()``
+    and runs under ``no_grad``. ``None`` (default) or ``len(features)``
+    freezes everything, with the whole base in one ``no_grad`` forward.
+    """
+
+    def __init__(self, base: nn.Module, fine_tune_at: Optional[int] = None):
         super().__init__()
         self.base = base
-        for p in self.base.parameters():
-            p.requires_grad = False
-        self.base.eval()
+        self.set_fine_tune_at(fine_tune_at)
+
+    def _num_features(self) -> Optional[int]:
+        feats = getattr(self.base, "features", None)
+        return len(feats) if isinstance(feats, nn.Sequential) else None
+
+    def set_fine_tune_at(self, fine_tune_at: Optional[int]) -> None:
+        n = self._num_features()
+        if fine_tune_at is None:
+            k = n
+        else:
+            if n is None:
+                raise ValueError("fine_tune_at needs a base with a `features` Sequential")
+            if (isinstance(fine_tune_at, bool) or not isinstance(fine_tune_at, int)
+                    or not 0 <= fine_tune_at <= n):
+                raise ValueError(
+                    f"fine_tune_at must be None or an int in [0, {n}], got {fine_tune_at!r}"
+                )
+            k = fine_tune_at
+        self._split = k  # == n (or None without `features`): fully frozen
+        if k is None or k == n:
+            for p in self.base.parameters():
+                p.requires_grad = False
+        else:
+            for i, m in enumerate(self.base.features):
+                for p in m.parameters():
+                    p.requires_grad = i >= k
+        self.train(self.training)
+
+    @property
+    def fine_tune_at(self) -> Optional[int]:
+        return self._split
+
+    def _fully_frozen(self) -> bool:
+        return self._split is None or self._split == self._num_features()
 
     def train(self, mode: bool = True) -> "FrozenBase":
-        # stay frozen: never switch the base to train-mode BN
         super().train(mode)
-        self.base.eval()
+        if self._fully_frozen():
+            # stay frozen: never switch the base to train-mode BN
+            self.base.eval()
+        else:
+            for m in self.base.features[: self._split]:
+                m.eval()
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._fully_frozen():
+            with torch.no_grad():
+                return self.base(x)
+        feats = self.base.features
         with torch.no_grad():
-            return self.base(x)
+            for m in feats[: self._split]:
+                x = m(x)
+        for m in feats[self._split:]:
+            x = m(x)
+        return x
 
 
 class TransferModel(nn.Module):
     """Frozen base -> GAP -> Dropout -> Dense(num_classes) logits
-    (reference ``.../02_model_training_single_node.py:171-176``)."""
+    (reference ``.../02_model_training_single_node.py:171-176``).
+    ``fine_tune_at``: see ``FrozenBase``."""
 
-    def __init__(self, channels: int = 3, num_classes: int = 5, dropout: float = 0.5):
+    def __init__(self, channels: int = 3, num_classes: int = 5, dropout: float = 0.5,
+                 fine_tune_at: Optional[int] = None):
         super().__init__()
-        self.base = FrozenBase(MobileNetV2(channels))
+        self.base = FrozenBase(MobileNetV2(channels), fine_tune_at)
         self.global_average_pooling = GlobalAvgPool2d()
         from ..ops.layers import Dropout as DdlwDropout
 
         self.dropout = DdlwDropout(dropout)  # K7 kernel on GPU, stock on CPU
         self.classifier = nn.Linear(1280, num_classes)
+
+    def set_fine_tune_at(self, fine_tune_at: Optional[int]) -> None:
+        """Switch the frozen/trainable split of the base in place (phase 2
+        after head training); a saved model keeps the new split. An
+        optimizer built earlier does not see newly trainable parameters."""
+        self.base.set_fine_tune_at(fine_tune_at)
+        spec = getattr(self, "_ddlw_builder_spec", None)
+        if spec is not None:
+            spec[1]["fine_tune_at"] = fine_tune_at
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = self.base(x)
@@ -141,8 +217,16 @@ def build_model(
     img_channels: int = 3,
     num_classes: int = 5,
     dropout: float = 0.5,
+    fine_tune_at: Optional[int] = None,
 ) -> TransferModel:
-    m = TransferModel(channels=img_channels, num_classes=num_classes, dropout=dropout)
+    """``fine_tune_at=k`` makes ``features[k:]`` of the MobileNetV2 base
+    trainable (23 children: 0-2 stem, 3-19 inverted residuals, 20-22 the
+    1x1 tail); ``None`` or 23 keeps the whole base frozen. The trainable
+    part follows the reference's per-layer ``trainable`` flags: its
+    BatchNorms use batch statistics in training (not Keras's
+    ``training=False`` fine-tuning recipe)."""
+    m = TransferModel(channels=img_channels, num_classes=num_classes, dropout=dropout,
+                      fine_tune_at=fine_tune_at)
     return tag_model(
         m,
         "mobilenet_v2_head",
@@ -152,5 +236,6 @@ def build_model(
             img_channels=img_channels,
             num_classes=num_classes,
             dropout=dropout,
+            fine_tune_at=fine_tune_at,
         ),
     )

@@ -126,11 +126,18 @@ def bn_grad_finalize_parts(part_db: torch.Tensor, part_dg: torch.Tensor,
 
 
 def bn_apply(x: torch.Tensor, res: Optional[torch.Tensor], mean, rstd, gamma, beta,
-             relu: bool):
+             relu):
     """Returns (y, mask): mask is a uint8 tensor of rows*C/8 relu bits (one
     byte per 8-channel vector) when relu, else None — backward reads the
-    mask instead of re-reading y."""
+    mask instead of re-reading y.
+
+    ``relu``: False/0 = identity, True/1 = ReLU, 2 = ReLU6. A mask bit means
+    "gradient passes here" (``0 < f < 6`` for ReLU6), so the backward
+    kernels take a ReLU6 layer as ``relu=True``."""
     lib = require_lib()
+    relu = int(relu)
+    if relu not in (0, 1, 2):
+        raise ValueError(f"bn_apply: relu mode must be 0, 1 or 2, got {relu}")
     rows, C = _rows_c(x)
     y = torch.empty_like(x)
     mask = (
@@ -142,7 +149,7 @@ def bn_apply(x: torch.Tensor, res: Optional[torch.Tensor], mean, rstd, gamma, be
         lib.ddlw_bn_apply(
             _nhwc_ptr(x), _p(res), _nhwc_ptr(y), _p(mask), _p(mean), _p(rstd),
             _p(gamma), _p(beta), ctypes.c_long(rows), ctypes.c_int(C),
-            ctypes.c_int(1 if relu else 0), ctypes.c_void_p(current_stream_ptr())
+            ctypes.c_int(relu), ctypes.c_void_p(current_stream_ptr())
         ),
         "bn_apply",
     )
@@ -326,6 +333,67 @@ def depthwise_fwd(x: torch.Tensor, weight: torch.Tensor, stride: int, padding: i
         "depthwise_fwd",
     )
     return y
+
+
+def _depthwise_w_t(weight: torch.Tensor) -> torch.Tensor:
+    c, _, r, s = weight.shape
+    w_t = weight.detach().reshape(c, r * s).t().contiguous()  # [R*S][C]
+    if w_t.dtype != torch.bfloat16:
+        w_t = w_t.to(torch.bfloat16)
+    return w_t
+
+
+def depthwise_dgrad(dy: torch.Tensor, weight: torch.Tensor, in_shape,
+                    stride: int, padding: int) -> torch.Tensor:
+    """Depthwise 3x3 conv2d input gradient. dy [N,C,Ho,Wo] channels_last
+    bf16, weight [C,1,3,3]; returns dx of ``in_shape`` (N,C,H,W),
+    channels_last bf16. Every dx element is written by the kernel."""
+    lib = require_lib()
+    n, c, h, w = in_shape
+    _, _, r, s = weight.shape
+    ho, wo = dy.shape[2], dy.shape[3]
+    assert dy.shape[0] == n and dy.shape[1] == c == weight.shape[0]
+    dx = torch.empty((n, c, h, w), dtype=torch.bfloat16, device=dy.device,
+                     memory_format=torch.channels_last)
+    check(
+        lib.ddlw_depthwise_dgrad(
+            _nhwc_ptr(dy), _p(_depthwise_w_t(weight)), _nhwc_ptr(dx),
+            n, h, w, c, ho, wo, r, s, stride, padding,
+            ctypes.c_void_p(current_stream_ptr())
+        ),
+        "depthwise_dgrad",
+    )
+    return dx
+
+
+@functools.lru_cache(maxsize=512)
+def _depthwise_wgrad_nparts(rows: int, C: int) -> int:
+    lib = require_lib()
+    return int(lib.ddlw_depthwise_wgrad_nparts(ctypes.c_long(rows), ctypes.c_int(C)))
+
+
+def depthwise_wgrad(dy: torch.Tensor, x: torch.Tensor, weight_shape,
+                    stride: int, padding: int) -> torch.Tensor:
+    """Depthwise 3x3 conv2d weight gradient, fp32 [C,1,3,3]. dy and x are
+    channels_last bf16. Two launches (row-slice partials, then a fixed-order
+    sum): no atomics, bit-reproducible."""
+    lib = require_lib()
+    n, c, h, w = x.shape
+    _, _, r, s = weight_shape
+    ho, wo = dy.shape[2], dy.shape[3]
+    assert dy.shape[0] == n and dy.shape[1] == c == weight_shape[0]
+    nparts = _depthwise_wgrad_nparts(n * ho * wo, c)
+    part = torch.empty(nparts, r * s, c, dtype=torch.float32, device=x.device)
+    dw = torch.empty((c, 1, r, s), dtype=torch.float32, device=x.device)
+    check(
+        lib.ddlw_depthwise_wgrad(
+            _nhwc_ptr(dy), _nhwc_ptr(x), _p(part), _p(dw),
+            n, h, w, c, ho, wo, r, s, stride, padding,
+            ctypes.c_void_p(current_stream_ptr())
+        ),
+        "depthwise_wgrad",
+    )
+    return dw
 
 
 def dropout_fwd(x: torch.Tensor, p: float, seed: int):

@@ -18,6 +18,38 @@ def conv_mode() -> str:
     return os.environ.get("DDLW_CONV", "auto")
 
 
+class _DepthwiseFn(torch.autograd.Function):
+    """Depthwise 3x3 conv (K2) with hand-written backward: forward is the
+    existing ``binding.depthwise_fwd``; backward launches the dgrad and
+    wgrad kernels, each only when its gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride: int, padding: int):
+        from . import binding
+
+        x = x.contiguous(memory_format=torch.channels_last)
+        ctx.save_for_backward(x, weight)
+        ctx.stride, ctx.padding = stride, padding
+        return binding.depthwise_fwd(x, weight, stride, padding)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import binding
+
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        if dy.dtype != torch.bfloat16:
+            dy = dy.to(torch.bfloat16)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = binding.depthwise_dgrad(dy, weight, x.shape, ctx.stride,
+                                         ctx.padding)
+        if ctx.needs_input_grad[1]:
+            dw = binding.depthwise_wgrad(dy, x, weight.shape, ctx.stride,
+                                         ctx.padding).to(weight.dtype)
+        return dx, dw, None, None
+
+
 class Conv2d(nn.Conv2d):
     """nn.Conv2d subclass so init/state_dict/bias handling are inherited;
     forward dispatches per policy. HIP implicit-GEMM path: ops.conv_gemm."""
@@ -48,6 +80,20 @@ class Conv2d(nn.Conv2d):
             pd = self.padding[0] if isinstance(self.padding, tuple) else self.padding
             return binding.depthwise_fwd(
                 x.contiguous(memory_format=torch.channels_last), self.weight, st, pd
+            )
+        if (
+            hip_ok
+            and self.groups == self.in_channels == self.out_channels
+            and self.in_channels % 8 == 0
+            and self.bias is None
+            and self.kernel_size == (3, 3)
+            and self.stride in ((1, 1), (2, 2))
+            and isinstance(self.padding, tuple)
+            and self.padding[0] == self.padding[1]
+        ):
+            # depthwise, trainable path: fwd kernel + dgrad/wgrad kernels
+            return _DepthwiseFn.apply(
+                x, self.weight, self.stride[0], self.padding[0]
             )
         if (
             hip_ok

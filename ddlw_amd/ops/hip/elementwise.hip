@@ -148,7 +148,8 @@ __global__ __launch_bounds__(256) void k_bn_finalize(
 // ---------------------------------------------------------------------------
 // BN apply (+ optional residual add, + optional ReLU), one fused pass:
 //   y = act((x - mean[c]) * rstd[c] * gamma[c] + beta[c] [+ res])
-// RELU: 0 = identity, 1 = relu. res may be null.
+// RELU: 0 = identity, 1 = relu, 2 = relu6 (mask bit = "gradient passes",
+// so the backward kernels take a relu6 layer as RELU = 1). res may be null.
 // ---------------------------------------------------------------------------
 // Geometry (shared with k_bn_bwd_dx): each thread owns ONE fixed 8-channel
 // vector column and streams rows, so the per-channel tables are loaded ONCE
@@ -187,7 +188,12 @@ __global__ __launch_bounds__(256) void k_bn_apply(
     for (int k = 0; k < 8; ++k) {
       float f = b2f(v.h[k]) * scale[k] + shift[k];
       if (HAS_RES) f += b2f(rv.h[k]);
-      if (RELU) {
+      if (RELU == 2) {
+        // ReLU6: gradient passes iff 0 < f < 6, decided on the fp32 value
+        // before bf16 rounding (hardtanh_backward's rule)
+        if (f > 0.f && f < 6.f) mb |= (1u << k);
+        f = fminf(fmaxf(f, 0.f), 6.f);
+      } else if (RELU) {
         if (f > 0.f) mb |= (1u << k);
         f = fmaxf(f, 0.f);
       }
@@ -788,7 +794,19 @@ DDLW_EXPORT int ddlw_bn_apply(const void* x, const void* res, void* y,
                               const void* gamma, const void* beta, long rows,
                               int C, int relu, void* stream) {
   dim3 grid = bn_ew_grid(rows, C);
-  if (relu && res)
+  if (relu == 2 && res)
+    hipLaunchKernelGGL((k_bn_apply<2, true>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)y,
+                       (unsigned char*)mask,
+                       (const float*)mean, (const float*)rstd, (const float*)gamma,
+                       (const float*)beta, rows, C);
+  else if (relu == 2)
+    hipLaunchKernelGGL((k_bn_apply<2, false>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, nullptr, (bf16_t*)y,
+                       (unsigned char*)mask,
+                       (const float*)mean, (const float*)rstd, (const float*)gamma,
+                       (const float*)beta, rows, C);
+  else if (relu && res)
     hipLaunchKernelGGL((k_bn_apply<1, true>), grid, dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)y,
                        (unsigned char*)mask,

@@ -47,7 +47,8 @@ def _cl(t: torch.Tensor) -> torch.Tensor:
 class _BnActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var,
-                training: bool, momentum: float, eps: float, relu: bool):
+                training: bool, momentum: float, eps: float, relu):
+        # relu: False/0 = identity, True/1 = ReLU, 2 = ReLU6
         x = _cl(x)
         if res is not None:
             res = _cl(res)
@@ -60,7 +61,8 @@ class _BnActFn(torch.autograd.Function):
         if mask is None:
             mask = x.new_empty(0, dtype=torch.uint8)
         ctx.save_for_backward(x, mask, mean, rstd, weight)
-        ctx.relu = relu
+        # the mask bit means "gradient passes", so backward treats ReLU6 as ReLU
+        ctx.relu = bool(relu)
         ctx.has_res = res is not None
         ctx.bn_training = training
         return y
@@ -85,20 +87,32 @@ class _BnActFn(torch.autograd.Function):
 
 
 class BatchNormAct2d(nn.Module):
-    """BatchNorm2d with optional fused residual-add and ReLU.
+    """BatchNorm2d with optional fused residual-add and ReLU / ReLU6.
 
     Replaces the reference's BN (+ReLU) pairs (kernels K4+K5)
     with ONE fused NHWC pass each way. Parameter/buffer names match
     nn.BatchNorm2d so state dicts interchange.
+
+    Activation: ``relu=True`` (as before) or ``act`` in ``ACTS``
+    (``"none"``, ``"relu"``, ``"relu6"``). ``act`` wins when given.
+    ``self.relu`` stays "a plain ReLU is fused here"; ``self.act`` names the
+    activation.
     """
 
+    ACTS = ("none", "relu", "relu6")
+
     def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1,
-                 relu: bool = False):
+                 relu: bool = False, act: Optional[str] = None):
         super().__init__()
+        if act is None:
+            act = "relu" if relu else "none"
+        if act not in self.ACTS:
+            raise ValueError(f"act must be one of {self.ACTS}, got {act!r}")
         self.num_features = num_features
         self.eps = eps
         self.momentum = momentum
-        self.relu = relu
+        self.act = act
+        self.relu = act == "relu"
         self.weight = nn.Parameter(torch.ones(num_features))
         self.bias = nn.Parameter(torch.zeros(num_features))
         self.register_buffer("running_mean", torch.zeros(num_features))
@@ -133,7 +147,8 @@ class BatchNormAct2d(nn.Module):
                 rm, rv = rm.float(), rv.float()
             return _BnActFn.apply(
                 x, residual, w, b, rm, rv,
-                self.training, self.momentum, self.eps, self.relu,
+                self.training, self.momentum, self.eps,
+                self.ACTS.index(self.act),
             )
         # stock fallback (CPU oracle / non-bf16 path)
         y = F.batch_norm(
@@ -143,7 +158,9 @@ class BatchNormAct2d(nn.Module):
         )
         if residual is not None:
             y = y + residual
-        return F.relu(y) if self.relu else y
+        if self.act == "relu6":
+            return F.relu6(y)
+        return F.relu(y) if self.act == "relu" else y
 
     def folded_scale_bias(self):
         """Eval-mode BN as one affine transform: y = x*scale + bias with
@@ -163,6 +180,8 @@ class BatchNormAct2d(nn.Module):
         return scale, bias
 
     def extra_repr(self) -> str:
+        if self.act == "relu6":
+            return f"{self.num_features}, act={self.act}"
         return f"{self.num_features}, relu={self.relu}"
 
 

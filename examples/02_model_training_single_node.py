@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--root", default=None)
     ap.add_argument("--epochs", type=int, default=EPOCHS)
     ap.add_argument("--img", type=int, default=IMG_HEIGHT)
+    ap.add_argument(
+        "--fine-tune-at", type=int, default=None, metavar="K",
+        help="also train MobileNetV2 features[K:] (0..23; default: frozen base)",
+    )
     args = ap.parse_args()
     setup(root=args.root)
 
@@ -50,7 +54,10 @@ def main():
 
     tracking.set_experiment("single_node_training")
     autolog()
-    model = Model(build_model(args.img, args.img, IMG_CHANNELS, num_classes))
+    model = Model(build_model(
+        args.img, args.img, IMG_CHANNELS, num_classes,
+        fine_tune_at=args.fine_tune_at,
+    ))
     model.compile(optimizer="Adam", learning_rate=1e-3, metrics=("accuracy",))
     with tracking.start_run(run_name="single_node") as run:
         hist = model.fit(
