@@ -28,8 +28,6 @@ for H, W, C, K, R, S, st, pad in shapes:
     res = {}
     for mode in ("0", "1"):
         os.environ["DDLW_CONV_WIDE"] = mode
-        import ctypes
-        conv_gemm.require_lib()  # reset static? env read once per proc... 
         y = conv_gemm.conv_fwd_kernel(x, w, st, pad)
         err = (y.float() - ref).abs().max().item() / (ref.abs().max().item() + 1e-6)
         for _ in range(3): conv_gemm.conv_fwd_kernel(x, w, st, pad)

@@ -2,7 +2,8 @@
 
 The implicit GPU-kernel inventory of the reference rebuilt
 as native HIP, built by ``ddlw_amd/ops/build.py`` (raw hipcc — no hipify, no
-CUDA path, no Triton) and bound via ctypes in ``binding.py``.
+CUDA path, no Triton) and bound via ctypes: ``abi.py`` holds the signature
+table, ``binding.py`` / ``conv_gemm.py`` the tensor-level wrappers.
 
 On a GPU box the HIP extension is REQUIRED: ops raise if the library is
 missing (no silent eager fallback; override only via DDLW_DISABLE_HIP_OPS=1).

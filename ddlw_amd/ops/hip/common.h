@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+#include <type_traits>
 
 #define DDLW_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -56,3 +57,23 @@ __device__ __forceinline__ float warp_reduce_max(float v) {
   } while (0)
 
 void ddlw_set_error(const char* msg);
+
+// launch dispatch -----------------------------------------------------------
+// Runtime value -> template argument: f is a generic lambda that receives a
+// std::integral_constant, so a launch statement is written once and
+// instantiated per listed value. with_int falls back to the LAST listed value.
+template <class F>
+static inline void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+template <int V, int... Rest, class F>
+static inline void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) {
+    f(std::integral_constant<int, V>{});
+  } else {
+    if (v == V) f(std::integral_constant<int, V>{});
+    else with_int<Rest...>(v, f);
+  }
+}

@@ -1038,16 +1038,25 @@ DDLW_EXPORT long ddlw_conv_fwd_nparts(int N, int C, int K, int Ho, int Wo,
   return cdiv(M, p.bm) * p.wvm;
 }
 
-static int conv_fwd_launch(const void* x, const void* w, void* y,
-                           const void* zpage, const void* acc,
-                           void* bn_ps, void* bn_pq,
-                           const void* bnb_x, const void* bnb_mask,
-                           const void* bnb_mean, const void* bnb_rstd,
-                           const void* ep_scale, const void* ep_bias,
-                           int ep_relu,
-                           int N, int H, int W_, int C, int K,
-                           int Ho, int Wo, int R, int S, int stride,
-                           int pad, int oH, int oW, int oS, void* stream) {
+// The one conv-forward entry point; a null pointer switches that fusion off.
+//   acc           y += acc (residual-join gradient add in conv1's dgrad)
+//   bn_ps/bn_pq   fused BN statistics: per-(tile_m, wave-row) sum/sumsq rows
+//   bnb_*         dgrad + fused BN-backward reduce: bn_ps/bn_pq receive the
+//                 (dbeta, dgamma) partials against (bnb_x, mask, mean, rstd),
+//                 so k_bn_bwd_reduce never re-reads dy
+//   ep_*          eval-mode BN fold: y = relu?(conv*scale[k] + bias[k] [+ acc])
+//   oH/oW/oS      output scatter geometry (Ho/Wo/1 for a plain conv)
+DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
+                                    const void* zpage, const void* acc,
+                                    void* bn_ps, void* bn_pq,
+                                    const void* bnb_x, const void* bnb_mask,
+                                    const void* bnb_mean, const void* bnb_rstd,
+                                    const void* ep_scale, const void* ep_bias,
+                                    int ep_relu,
+                                    int N, int H, int W_, int C, int K,
+                                    int Ho, int Wo, int R, int S, int stride,
+                                    int pad, int oH, int oW, int oS,
+                                    void* stream) {
   if (C % 64 != 0) {
     ddlw_set_error("conv_fwd_igemm: C must be a multiple of 64");
     return 2;
@@ -1086,116 +1095,27 @@ static int conv_fwd_launch(const void* x, const void* w, void* y,
 #undef WIDE_LAUNCH
     DDLW_CHECK_LAUNCH();
   }
-#define LAUNCH(BM, BN, EPI, BUFS)                                             \
-  do {                                                                        \
-    long grid = cdiv(M, BM) * cdiv(K, BN);                                    \
-    if (!p.m32)                                                               \
-      hipLaunchKernelGGL((k_conv_fwd_igemm<BM, BN, EPI, BUFS, false>),        \
-                         dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x, \
-                         (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage,  \
-                         N, H, W_, C, K, Ho, Wo, R, S, stride, pad,           \
-                         (int)grid, oH, oW, oS, mg_wo, sh_wo, mg_ho, sh_ho,   \
-                         (const bf16_t*)acc, (float*)bn_ps, (float*)bn_pq,    \
-                         (const bf16_t*)bnb_x,                                \
-                         (const unsigned char*)bnb_mask,                      \
-                         (const float*)bnb_mean, (const float*)bnb_rstd,      \
-                         (const float*)ep_scale, (const float*)ep_bias,       \
-                         ep_relu);                                            \
-    else                                                                      \
-      hipLaunchKernelGGL((k_conv_fwd_igemm<BM, BN, EPI, BUFS, true>),         \
-                         dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x, \
-                         (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage,  \
-                         N, H, W_, C, K, Ho, Wo, R, S, stride, pad,           \
-                         (int)grid, oH, oW, oS, mg_wo, sh_wo, mg_ho, sh_ho,   \
-                         (const bf16_t*)acc, (float*)bn_ps, (float*)bn_pq,    \
-                         (const bf16_t*)bnb_x,                                \
-                         (const unsigned char*)bnb_mask,                      \
-                         (const float*)bnb_mean, (const float*)bnb_rstd,      \
-                         (const float*)ep_scale, (const float*)ep_bias,       \
-                         ep_relu);                                            \
-  } while (0)
-  if (p.bn == 128) {
-    if (p.epi_lds) {
-      if (p.bufs == 1) LAUNCH(128, 128, true, 1);
-      else LAUNCH(128, 128, true, 2);
-    } else {
-      if (p.bufs == 1) LAUNCH(128, 128, false, 1);
-      else LAUNCH(128, 128, false, 2);
-    }
-  } else if (p.bn == 64) {
-    if (p.epi_lds) {
-      if (p.bufs == 1) LAUNCH(128, 64, true, 1);
-      else LAUNCH(128, 64, true, 2);
-    } else {
-      if (p.bufs == 1) LAUNCH(128, 64, false, 1);
-      else LAUNCH(128, 64, false, 2);
-    }
-  } else {
-    if (p.epi_lds) {
-      if (p.bufs == 1) LAUNCH(128, 32, true, 1);
-      else LAUNCH(128, 32, true, 2);
-    } else {
-      if (p.bufs == 1) LAUNCH(128, 32, false, 1);
-      else LAUNCH(128, 32, false, 2);
-    }
-  }
-#undef LAUNCH
+  with_int<128, 64, 32>(p.bn, [&](auto BN) {
+    with_bool(p.epi_lds, [&](auto EPI) {
+      with_int<1, 2>(p.bufs, [&](auto BUFS) {
+        with_bool(p.m32, [&](auto M32) {
+          long grid = cdiv(M, 128) * cdiv(K, decltype(BN)::value);
+          hipLaunchKernelGGL(
+              (k_conv_fwd_igemm<128, decltype(BN)::value, decltype(EPI)::value,
+                                decltype(BUFS)::value, decltype(M32)::value>),
+              dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x,
+              (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage, N, H, W_, C,
+              K, Ho, Wo, R, S, stride, pad, (int)grid, oH, oW, oS, mg_wo,
+              sh_wo, mg_ho, sh_ho, (const bf16_t*)acc, (float*)bn_ps,
+              (float*)bn_pq, (const bf16_t*)bnb_x,
+              (const unsigned char*)bnb_mask, (const float*)bnb_mean,
+              (const float*)bnb_rstd, (const float*)ep_scale,
+              (const float*)ep_bias, ep_relu);
+        });
+      });
+    });
+  });
   DDLW_CHECK_LAUNCH();
-}
-
-DDLW_EXPORT int ddlw_conv_fwd_igemm_acc(const void* x, const void* w, void* y,
-                                        const void* zpage, const void* acc,
-                                        int N, int H, int W_, int C, int K,
-                                        int Ho, int Wo, int R, int S, int stride,
-                                        int pad, int oH, int oW, int oS,
-                                        void* stream) {
-  return conv_fwd_launch(x, w, y, zpage, acc, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, H,
-                         W_, C, K, Ho, Wo, R, S, stride, pad, oH, oW, oS,
-                         stream);
-}
-
-DDLW_EXPORT int ddlw_conv_fwd_igemm_stats(const void* x, const void* w, void* y,
-                                          const void* zpage,
-                                          void* bn_ps, void* bn_pq,
-                                          int N, int H, int W_, int C, int K,
-                                          int Ho, int Wo, int R, int S,
-                                          int stride, int pad, void* stream) {
-  return conv_fwd_launch(x, w, y, zpage, nullptr, bn_ps, bn_pq, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, H,
-                         W_, C, K, Ho, Wo, R, S, stride, pad, Ho, Wo, 1,
-                         stream);
-}
-
-// dgrad + fused BN-backward reduce: y = dgrad output (the BN's dy); the
-// epilogue also emits (dbeta, dgamma) partials against (bnb_x, mask,
-// mean, rstd) so k_bn_bwd_reduce never re-reads dy.
-DDLW_EXPORT int ddlw_conv_fwd_igemm_bnb(
-    const void* x, const void* w, void* y, const void* zpage, const void* acc,
-    const void* bnb_x, const void* bnb_mask, const void* bnb_mean,
-    const void* bnb_rstd, void* p_db, void* p_dg,
-    int N, int H, int W_, int C, int K, int Ho, int Wo, int R, int S,
-    int stride, int pad, void* stream) {
-  return conv_fwd_launch(x, w, y, zpage, acc, p_db, p_dg, bnb_x, bnb_mask,
-                         bnb_mean, bnb_rstd, nullptr, nullptr, 0, N, H, W_, C,
-                         K, Ho, Wo, R, S, stride, pad, Ho, Wo, 1, stream);
-}
-
-// fwd + fused eval-mode BN apply: y = relu?(conv*scale[k] + bias[k] [+ acc])
-// — scale/bias are the host-folded running-stat BN transform, so the whole
-// bn_apply pass disappears from inference/eval (and the acc input carries
-// the residual shortcut for the bn3-join).
-DDLW_EXPORT int ddlw_conv_fwd_igemm_ep(const void* x, const void* w, void* y,
-                                       const void* zpage, const void* acc,
-                                       const void* ep_scale, const void* ep_bias,
-                                       int ep_relu,
-                                       int N, int H, int W_, int C, int K,
-                                       int Ho, int Wo, int R, int S,
-                                       int stride, int pad, void* stream) {
-  return conv_fwd_launch(x, w, y, zpage, acc, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, ep_scale, ep_bias, ep_relu,
-                         N, H, W_, C, K, Ho, Wo, R, S, stride, pad, Ho, Wo, 1,
-                         stream);
 }
 
 // merged-class stride-2 3x3 dgrad (even ih/iw): dx = scattered union of 4
@@ -1228,40 +1148,18 @@ DDLW_EXPORT int ddlw_conv_dgrad_s2m(const void* dy, const void* wcat, void* dx,
     const char* e = getenv("DDLW_S2_EPI");
     if (e && e[0] == '0') s2epi = 0;
   }
-#define S2LAUNCH(BN_)                                                          \
-  do {                                                                         \
-    long gx = cdiv(M, 128) * cdiv(Cdx, BN_);                                   \
-    if (!s2epi)                                                                \
-      hipLaunchKernelGGL((k_conv_fwd_igemm<128, BN_, false, 2, false>),        \
-                         dim3((int)gx, 4), dim3(256), 0, st,                   \
-                         (const bf16_t*)dy, (const bf16_t*)wcat, (bf16_t*)dx,  \
-                         (const bf16_t*)zpage, N, Ho, Wo, Kdy, Cdx, oh, ow, 2, \
-                         2, 1, 0, (int)gx, ih, iw, 2, mg_wo, sh_wo, mg_ho,     \
-                         sh_ho, nullptr, nullptr, nullptr, nullptr, nullptr,   \
-                         nullptr, nullptr, nullptr, nullptr, 0, 1, q);         \
-    else                                                                       \
-      hipLaunchKernelGGL((k_conv_fwd_igemm<128, BN_, true, 2, false>),         \
-                       dim3((int)gx, 4), dim3(256), 0, st, (const bf16_t*)dy,  \
-                       (const bf16_t*)wcat, (bf16_t*)dx, (const bf16_t*)zpage, \
-                       N, Ho, Wo, Kdy, Cdx, oh, ow, 2, 2, 1, 0, (int)gx, ih,   \
-                       iw, 2, mg_wo, sh_wo, mg_ho, sh_ho, nullptr, nullptr,    \
-                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,   \
-                       nullptr, 0, 1, q);     \
-  } while (0)
-  if (Cdx >= 128)
-    S2LAUNCH(128);
-  else
-    S2LAUNCH(64);
-#undef S2LAUNCH
+  with_bool(Cdx >= 128, [&](auto WIDE_N) {
+    with_bool(s2epi != 0, [&](auto EPI) {
+      constexpr int BN = decltype(WIDE_N)::value ? 128 : 64;
+      long gx = cdiv(M, 128) * cdiv(Cdx, BN);
+      hipLaunchKernelGGL(
+          (k_conv_fwd_igemm<128, BN, decltype(EPI)::value, 2, false>),
+          dim3((int)gx, 4), dim3(256), 0, st, (const bf16_t*)dy,
+          (const bf16_t*)wcat, (bf16_t*)dx, (const bf16_t*)zpage, N, Ho, Wo,
+          Kdy, Cdx, oh, ow, 2, 2, 1, 0, (int)gx, ih, iw, 2, mg_wo, sh_wo,
+          mg_ho, sh_ho, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+          nullptr, nullptr, nullptr, 0, 1, q);
+    });
+  });
   DDLW_CHECK_LAUNCH();
-}
-
-DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
-                                    const void* zpage,
-                                    int N, int H, int W_, int C, int K,
-                                    int Ho, int Wo, int R, int S, int stride,
-                                    int pad, int oH, int oW, int oS,
-                                    void* stream) {
-  return ddlw_conv_fwd_igemm_acc(x, w, y, zpage, nullptr, N, H, W_, C, K, Ho,
-                                 Wo, R, S, stride, pad, oH, oW, oS, stream);
 }

@@ -703,18 +703,6 @@ DDLW_EXPORT int ddlw_bn_stats(const void* x, void* part_sum, void* part_sumsq,
   DDLW_CHECK_LAUNCH();
 }
 
-DDLW_EXPORT int ddlw_bn_finalize(const void* part_sum, const void* part_sumsq,
-                                 void* mean, void* rstd, void* rmean, void* rvar,
-                                 long rows, int C, float eps, float momentum,
-                                 void* stream) {
-  hipLaunchKernelGGL(k_bn_finalize, dim3((C + 31) / 32), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)part_sum,
-                     (const float*)part_sumsq, (float*)mean, (float*)rstd,
-                     (float*)rmean, (float*)rvar, rows, C,
-                     ddlw_bn_nparts(rows, C), eps, momentum);
-  DDLW_CHECK_LAUNCH();
-}
-
 // Fold a LARGE partial set (conv-epilogue fused stats: nparts = grid_m x
 // waves_m, up to ~12k rows) down to G rows with a chip-filling grid —
 // k_bn_finalize's grid is only ceil(C/32) blocks (2 for C=64) and would
@@ -759,12 +747,13 @@ DDLW_EXPORT int ddlw_bn_parts_fold(const void* ps, const void* pq, void* os,
   DDLW_CHECK_LAUNCH();
 }
 
-// finalize over an EXPLICIT partial count (conv-epilogue fused stats write
-// grid_m * waves_m partial rows, not ddlw_bn_nparts's geometry)
-DDLW_EXPORT int ddlw_bn_finalize_n(const void* part_sum, const void* part_sumsq,
-                                   void* mean, void* rstd, void* rmean,
-                                   void* rvar, long rows, int C, int nparts,
-                                   float eps, float momentum, void* stream) {
+// finalize over the caller's partial count: ddlw_bn_nparts(rows, C) after
+// ddlw_bn_stats, grid_m * waves_m (or the fold's G) after conv-epilogue
+// fused stats
+DDLW_EXPORT int ddlw_bn_finalize(const void* part_sum, const void* part_sumsq,
+                                 void* mean, void* rstd, void* rmean,
+                                 void* rvar, long rows, int C, int nparts,
+                                 float eps, float momentum, void* stream) {
   hipLaunchKernelGGL(k_bn_finalize, dim3((C + 31) / 32), dim3(256), 0,
                      (hipStream_t)stream, (const float*)part_sum,
                      (const float*)part_sumsq, (float*)mean, (float*)rstd,
@@ -772,7 +761,6 @@ DDLW_EXPORT int ddlw_bn_finalize_n(const void* part_sum, const void* part_sumsq,
                      momentum);
   DDLW_CHECK_LAUNCH();
 }
-
 
 // grid for the fixed-channel elementwise BN kernels: x covers channel-vector
 // groups, y covers row groups (capped; kernels stride the remainder)
@@ -794,42 +782,15 @@ DDLW_EXPORT int ddlw_bn_apply(const void* x, const void* res, void* y,
                               const void* gamma, const void* beta, long rows,
                               int C, int relu, void* stream) {
   dim3 grid = bn_ew_grid(rows, C);
-  if (relu == 2 && res)
-    hipLaunchKernelGGL((k_bn_apply<2, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)y,
-                       (unsigned char*)mask,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)beta, rows, C);
-  else if (relu == 2)
-    hipLaunchKernelGGL((k_bn_apply<2, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, nullptr, (bf16_t*)y,
-                       (unsigned char*)mask,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)beta, rows, C);
-  else if (relu && res)
-    hipLaunchKernelGGL((k_bn_apply<1, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)y,
-                       (unsigned char*)mask,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)beta, rows, C);
-  else if (relu)
-    hipLaunchKernelGGL((k_bn_apply<1, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, nullptr, (bf16_t*)y,
-                       (unsigned char*)mask,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)beta, rows, C);
-  else if (res)
-    hipLaunchKernelGGL((k_bn_apply<0, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)y,
-                       (unsigned char*)mask,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)beta, rows, C);
-  else
-    hipLaunchKernelGGL((k_bn_apply<0, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, nullptr, (bf16_t*)y,
-                       (unsigned char*)mask,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)beta, rows, C);
+  with_int<2, 0, 1>(relu, [&](auto RELU) {  // any other nonzero mode = ReLU
+    with_bool(res != nullptr, [&](auto RES) {
+      hipLaunchKernelGGL((k_bn_apply<decltype(RELU)::value, decltype(RES)::value>),
+                         grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                         (const bf16_t*)res, (bf16_t*)y, (unsigned char*)mask,
+                         (const float*)mean, (const float*)rstd,
+                         (const float*)gamma, (const float*)beta, rows, C);
+    });
+  });
   DDLW_CHECK_LAUNCH();
 }
 
@@ -840,33 +801,19 @@ DDLW_EXPORT int ddlw_bn_bwd_reduce(const void* dy, const void* mask, const void*
   int vecC = C >> 3;
   int VPB = vecC < 256 ? vecC : 256;
   dim3 grid((vecC + VPB - 1) / VPB, ddlw_bn_nparts(rows, C));
-  if (relu)
-    hipLaunchKernelGGL((k_bn_bwd_reduce<1>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const unsigned char*)mask, (const bf16_t*)x,
+  with_int<0, 1>(relu, [&](auto RELU) {
+    hipLaunchKernelGGL((k_bn_bwd_reduce<decltype(RELU)::value>), grid,
+                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
+                       (const unsigned char*)mask, (const bf16_t*)x,
                        (const float*)mean, (const float*)rstd, (float*)dbeta,
                        (float*)dgamma, rows, C);
-  else
-    hipLaunchKernelGGL((k_bn_bwd_reduce<0>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const unsigned char*)mask, (const bf16_t*)x,
-                       (const float*)mean, (const float*)rstd, (float*)dbeta,
-                       (float*)dgamma, rows, C);
+  });
   DDLW_CHECK_LAUNCH();
 }
 
 DDLW_EXPORT int ddlw_bn_grad_finalize(const void* part_db, const void* part_dg,
-                                      void* dbeta, void* dgamma, long rows,
-                                      int C, void* stream) {
-  hipLaunchKernelGGL(k_bn_grad_finalize, dim3((C + 31) / 32), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)part_db,
-                     (const float*)part_dg, (float*)dbeta, (float*)dgamma, C,
-                     ddlw_bn_nparts(rows, C));
-  DDLW_CHECK_LAUNCH();
-}
-
-DDLW_EXPORT int ddlw_bn_grad_finalize_n(const void* part_db,
-                                        const void* part_dg, void* dbeta,
-                                        void* dgamma, int C, int nparts,
-                                        void* stream) {
+                                      void* dbeta, void* dgamma, int C,
+                                      int nparts, void* stream) {
   hipLaunchKernelGGL(k_bn_grad_finalize, dim3((C + 31) / 32), dim3(256), 0,
                      (hipStream_t)stream, (const float*)part_db,
                      (const float*)part_dg, (float*)dbeta, (float*)dgamma, C,
@@ -880,30 +827,17 @@ DDLW_EXPORT int ddlw_bn_bwd_dx(const void* dy, const void* mask, const void* x,
                                const void* dgamma, void* dx, void* dres,
                                long rows, int C, int relu, void* stream) {
   dim3 grid = bn_ew_grid(rows, C);
-  if (relu && dres)
-    hipLaunchKernelGGL((k_bn_bwd_dx<1, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const unsigned char*)mask, (const bf16_t*)x,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)dbeta, (const float*)dgamma, (bf16_t*)dx,
-                       (bf16_t*)dres, rows, C);
-  else if (relu)
-    hipLaunchKernelGGL((k_bn_bwd_dx<1, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const unsigned char*)mask, (const bf16_t*)x,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)dbeta, (const float*)dgamma, (bf16_t*)dx,
-                       nullptr, rows, C);
-  else if (dres)
-    hipLaunchKernelGGL((k_bn_bwd_dx<0, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const unsigned char*)mask, (const bf16_t*)x,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)dbeta, (const float*)dgamma, (bf16_t*)dx,
-                       (bf16_t*)dres, rows, C);
-  else
-    hipLaunchKernelGGL((k_bn_bwd_dx<0, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const unsigned char*)mask, (const bf16_t*)x,
-                       (const float*)mean, (const float*)rstd, (const float*)gamma,
-                       (const float*)dbeta, (const float*)dgamma, (bf16_t*)dx,
-                       nullptr, rows, C);
+  with_int<0, 1>(relu, [&](auto RELU) {
+    with_bool(dres != nullptr, [&](auto DRES) {
+      hipLaunchKernelGGL((k_bn_bwd_dx<decltype(RELU)::value, decltype(DRES)::value>),
+                         grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
+                         (const unsigned char*)mask, (const bf16_t*)x,
+                         (const float*)mean, (const float*)rstd,
+                         (const float*)gamma, (const float*)dbeta,
+                         (const float*)dgamma, (bf16_t*)dx, (bf16_t*)dres,
+                         rows, C);
+    });
+  });
   DDLW_CHECK_LAUNCH();
 }
 

@@ -4,9 +4,10 @@ The library is built by ``ddlw_amd/ops/build.py`` (raw ``hipcc
 --offload-arch=gfx950 -shared -fPIC``) into ``ddlw_amd/ops/`` so it travels
 with the repo snapshot to GPU boxes. Kernels are exposed as ``extern "C"``
 functions taking raw device pointers + the current HIP stream; Python binds
-them with ctypes — torch tensors supply ``data_ptr()`` and
-``torch.cuda.current_stream().cuda_stream`` supplies the stream, so kernels
-land on the same stream PyTorch uses (and are capturable in hipGraphs).
+them with ctypes through the one signature table in ``abi.py`` — torch
+tensors supply ``data_ptr()`` and ``torch.cuda.current_stream().cuda_stream``
+supplies the stream (``launch`` appends it), so kernels land on the same
+stream PyTorch uses (and are capturable in hipGraphs).
 """
 from __future__ import annotations
 
@@ -16,6 +17,8 @@ from pathlib import Path
 from typing import Optional
 
 import torch
+
+from . import abi
 
 LIB_NAME = "libddlw_kernels.so"
 LIB_DIR = Path(__file__).resolve().parent
@@ -38,11 +41,18 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _load_error = f"{path} not built (run ddlw_amd/ops/build.py)"
         return None
     try:
-        _lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
+        cdll = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as e:
         _load_error = f"failed to load {path}: {e}"
         return None
-    _lib.ddlw_last_error.restype = ctypes.c_char_p
+
+    def missing(name):
+        raise KernelLibError(
+            f"{path} does not export {name} (stale build? run "
+            "`python -m ddlw_amd.ops.build`)")
+
+    abi.apply(cdll, missing)
+    _lib = cdll
     return _lib
 
 
@@ -74,6 +84,20 @@ def check(status: int, name: str) -> None:
 
 def current_stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def launch(name: str, *args) -> None:
+    """Call the launching export ``ddlw_<name>(*args, stream)`` on torch's
+    current stream and raise KernelLibError on a nonzero status. Arguments
+    are converted by the ``abi`` table: tensors/None for pointers, plain
+    ints and floats for the rest."""
+    fn = getattr(require_lib(), "ddlw_" + name)
+    check(fn(*args, current_stream_ptr()), name)
+
+
+def query(name: str, *args):
+    """Call a non-launching export (the ``*_nparts`` geometry queries)."""
+    return getattr(require_lib(), "ddlw_" + name)(*args)
 
 
 def on_gpu(*tensors: torch.Tensor) -> bool:

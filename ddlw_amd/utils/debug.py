@@ -38,14 +38,11 @@ def device_sync_each_op():
     chasing a miscompare)."""
     from ..ops import runtime
 
-    lib = runtime.lib()
     prev = runtime.check
 
     def checked(status, name):
         prev(status, name)
-        if lib is not None:
-            if lib.ddlw_device_sync() != 0:
-                raise RuntimeError(f"device fault after {name}: {lib.ddlw_last_error().decode()}")
+        prev(runtime.query("device_sync"), f"device sync after {name}")
 
     runtime.check = checked
     try:

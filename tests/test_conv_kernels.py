@@ -39,7 +39,12 @@ def test_conv_fwd_kernel_parity(shape):
     assert ((y - ref).abs().max() / scale).item() < 5e-2
 
 
-@pytest.mark.parametrize("shape", [s for s in SHAPES if s[6] == 1] + [(14, 14, 64, 64, 3, 3, 2)])
+@pytest.mark.parametrize("shape", [s for s in SHAPES if s[6] == 1] + [
+    (14, 14, 64, 64, 3, 3, 2),
+    (15, 15, 64, 64, 3, 3, 2),    # odd size: four-launch parity path
+    (14, 14, 64, 128, 1, 1, 2),   # 1x1 stride-2 scatter epilogue
+    (15, 15, 64, 128, 1, 1, 2),   # ... odd size
+])
 def test_conv_dgrad_kernel_parity(shape):
     from ddlw_amd.ops import conv_gemm
 
@@ -311,6 +316,41 @@ def test_conv_fused_bn_stats_parity(shape):
     # the conv output itself unchanged vs the stats-free launch
     y2 = conv_gemm.conv_fwd_kernel(x, w, st, pad)
     assert torch.equal(y, y2)
+
+
+@pytest.mark.parametrize("C", [64, 72])
+@pytest.mark.parametrize("nparts", [512, 513])  # 513: staged through bn_parts_fold
+def test_bn_finalize_parts_synthetic(nparts, C):
+    """bn_finalize_parts / bn_grad_finalize_parts on synthetic partials, on
+    both sides of the shared fold helper's nparts > 512 threshold. Reference
+    in float64 from the rows themselves; running stats as k_bn_finalize
+    (momentum 0.1, unbiased variance)."""
+    from ddlw_amd.ops import binding
+
+    torch.manual_seed(5)
+    rows = nparts * 4
+    X = torch.randn(rows, C, device=_cuda()) + 1
+    Xp = X.view(nparts, 4, C)
+    rm = torch.zeros(C, device=_cuda())
+    rv = torch.ones(C, device=_cuda())
+    mean, rstd = binding.bn_finalize_parts(
+        Xp.sum(1).contiguous(), Xp.square().sum(1).contiguous(), nparts, rows,
+        C, 1e-5, 0.1, rm, rv)
+    X64 = X.double()
+    mean_ref = X64.mean(0)
+    var_ref = (X64.square().mean(0) - mean_ref.square()).clamp_min(0)
+    rstd_ref = 1 / torch.sqrt(var_ref + 1e-5)
+    for got, ref in ((mean, mean_ref), (rstd, rstd_ref), (rm, 0.1 * mean_ref),
+                     (rv, 0.9 + 0.1 * var_ref * rows / (rows - 1))):
+        assert torch.allclose(got.double(), ref, atol=1e-3, rtol=1e-3), \
+            (got.double() - ref).abs().max()
+
+    pdb = torch.randn(nparts, C, device=_cuda())
+    pdg = torch.randn(nparts, C, device=_cuda())
+    dbeta, dgamma = binding.bn_grad_finalize_parts(pdb, pdg, nparts, C)
+    for got, ref in ((dbeta, pdb.double().sum(0)), (dgamma, pdg.double().sum(0))):
+        assert torch.allclose(got.double(), ref, atol=1e-3, rtol=1e-3), \
+            (got.double() - ref).abs().max()
 
 
 def test_stem_conv_parity():
