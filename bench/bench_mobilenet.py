@@ -1,0 +1,276 @@
+#!/usr/bin/env python3
+"""Frozen-MobileNetV2 benchmark: the fused pointwise / depthwise kernels vs
+the unfused path (library conv or ``depthwise_fwd``, then the
+``BatchNormAct2d`` eval forward, then the eager residual add where the block
+has one), per layer and end to end.
+
+Method of ``bench_depthwise.py``: one process, the two contenders alternate
+round by round, device events around ``--iters`` back-to-back calls, median
+over ``--rounds`` rounds. ``spread`` is max - min of the unfused contender's
+rounds. Routing rule (docs/KERNELS.md): a shape stays on the fused kernel
+only if its median beats the unfused median by more than that spread;
+``keep`` in each record says so.
+
+End to end, fused on vs ``DDLW_EVAL_FOLD=0`` (read at call time):
+  - frozen ``MobileNetV2`` forward at 224, bf16, img/s;
+  - one head-training step of ``build_model(224, 224, 3, 5)``: forward, CE,
+    backward, Adam.
+
+Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
+Prints one JSON line per layer shape, a table, and one final JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+from ddlw_amd.models.mobilenet_v2 import _V2_CFG, MobileNetV2, build_model  # noqa: E402
+from ddlw_amd.ops import FusedAdam, binding, softmax_cross_entropy  # noqa: E402
+from ddlw_amd.ops.conv import Conv2d  # noqa: E402
+from ddlw_amd.ops.layers import BatchNormAct2d  # noqa: E402
+
+ACTS = ("none", "relu", "relu6")
+
+
+def layer_shapes(size: int = 224):
+    """Distinct pointwise (H, C, K, act, res) and depthwise (H, C, stride)
+    layers of MobileNetV2 at ``size`` input, in network order."""
+    pw, dw = [], []
+
+    def add(lst, item):
+        if item not in lst:
+            lst.append(item)
+
+    h, in_ch = size // 2, 32
+    for t, c, n, s in _V2_CFG:
+        for i in range(n):
+            stride = s if i == 0 else 1
+            hidden = in_ch * t
+            if t != 1:
+                add(pw, (h, in_ch, hidden, 2, False))
+            add(dw, (h, hidden, stride))
+            h = (h + 2 - 3) // stride + 1
+            add(pw, (h, hidden, c, 0, stride == 1 and in_ch == c))
+            in_ch = c
+    add(pw, (h, in_ch, 1280, 2, False))
+    return pw, dw
+
+
+def _cl(t):
+    return t.contiguous(memory_format=torch.channels_last)
+
+
+def _round_ms(fn, iters: int) -> float:
+    start = torch.cuda.Event(enable_timing=True)
+    stop = torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) / iters
+
+
+def time_interleaved(fns: dict, iters: int, rounds: int, warmup: int = 3) -> dict:
+    """{name: [ms per round]}; the variants alternate round by round."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            samples[k].append(_round_ms(fn, iters))
+    return samples
+
+
+def _verdict(samples: dict) -> dict:
+    fused, unfused = samples["fused"], samples["unfused"]
+    mf, mu = statistics.median(fused), statistics.median(unfused)
+    spread = max(unfused) - min(unfused)
+    return {"ms_fused": round(mf, 4), "ms_unfused": round(mu, 4),
+            "ms_min_fused": round(min(fused), 4),
+            "spread_unfused": round(spread, 4),
+            "speedup": round(mu / mf, 2), "keep": bool(mu - mf > spread)}
+
+
+def _bn(c, act, dev):
+    bn = BatchNormAct2d(c, act=ACTS[act]).to(dev).eval()
+    with torch.no_grad():
+        bn.running_mean.uniform_(-0.3, 0.3)
+        bn.running_var.uniform_(0.5, 1.5)
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.2, 0.2)
+    return bn
+
+
+def bench_pointwise(B, H, C, K, act, res, dev, iters, rounds):
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    conv = Conv2d(C, K, 1, bias=False).to(dev).to(torch.bfloat16).eval()
+    bn = _bn(K, act, dev)
+    r = _cl(torch.randn(B, K, H, H, device=dev).to(torch.bfloat16)) if res else None
+    scale, bias = bn.folded_scale_bias()
+
+    def fused():
+        return binding.pw_conv_fwd(x, conv.weight, scale, bias, act, r)
+
+    def unfused():
+        y = bn(conv(x))
+        return r + y if res else y
+
+    with torch.no_grad():
+        ref = unfused().float()
+        err = ((fused().float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
+        rec = _verdict(time_interleaved({"fused": fused, "unfused": unfused},
+                                        iters, rounds))
+    M = B * H * H
+    bytes_io = 2.0 * M * (C + K * (2 if res else 1))
+    rec = {"kind": "pointwise", "shape": f"m{M}_c{C}_k{K}", "M": M, "C": C,
+           "K": K, "act": act, "res": res, "rel_err_vs_unfused": round(err, 5),
+           **rec, "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)}
+    return rec
+
+
+def bench_depthwise(B, H, C, stride, dev, iters, rounds):
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    w = torch.randn(C, 1, 3, 3, device=dev).to(torch.bfloat16)
+    bn = _bn(C, 2, dev)
+    scale, bias = bn.folded_scale_bias()
+
+    def fused():
+        return binding.depthwise_fwd_ep(x, w, scale, bias, 2, stride, 1)
+
+    def unfused():
+        return bn(binding.depthwise_fwd(x, w, stride, 1))
+
+    with torch.no_grad():
+        ref = unfused().float()
+        err = ((fused().float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
+        rec = _verdict(time_interleaved({"fused": fused, "unfused": unfused},
+                                        iters, rounds))
+    Ho = (H + 2 - 3) // stride + 1
+    bytes_io = 2.0 * B * C * (H * H + Ho * Ho)
+    return {"kind": "depthwise", "shape": f"n{B}_h{H}_c{C}_s{stride}",
+            "rel_err_vs_unfused": round(err, 5), **rec,
+            "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)}
+
+
+def _bf16_convs(m):
+    m = m.to(memory_format=torch.channels_last)
+    for mod in m.modules():
+        if isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear)):
+            mod.to(torch.bfloat16)
+    return m
+
+
+def _with_fold(value, fn):
+    def run():
+        os.environ["DDLW_EVAL_FOLD"] = value
+        try:
+            return fn()
+        finally:
+            os.environ.pop("DDLW_EVAL_FOLD", None)
+    return run
+
+
+def bench_end_to_end(B, dev, iters, rounds):
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
+    labels = torch.randint(0, 5, (B,), device=dev)
+    base = _bf16_convs(MobileNetV2().to(dev)).eval()
+
+    def fwd():
+        with torch.no_grad():
+            return base(x)
+
+    s = time_interleaved({"fused": _with_fold("1", fwd),
+                          "unfused": _with_fold("0", fwd)}, iters, rounds)
+    out = {"base_fwd": _verdict(s)}
+    for k in ("fused", "unfused"):
+        out["base_fwd"][f"img_s_{k}"] = round(B / out["base_fwd"][f"ms_{k}"] * 1e3, 1)
+    del base
+
+    model = _bf16_convs(build_model(224, 224, 3, 5).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    s = time_interleaved({"fused": _with_fold("1", step),
+                          "unfused": _with_fold("0", step)}, iters, rounds)
+    out["head_step"] = _verdict(s)
+    for k in ("fused", "unfused"):
+        out["head_step"][f"img_s_{k}"] = round(B / out["head_step"][f"ms_{k}"] * 1e3, 1)
+    return out
+
+
+def _table(recs):
+    print(f"{'kind':10s} {'shape':24s} {'fused ms':>9s} {'unfused ms':>10s} "
+          f"{'spread':>8s} {'speedup':>8s} {'GB/s':>8s} keep")
+    for r in recs:
+        print(f"{r['kind']:10s} {r['shape']:24s} {r['ms_fused']:9.4f} "
+              f"{r['ms_unfused']:10.4f} {r['spread_unfused']:8.4f} "
+              f"{r['speedup']:8.2f} {r['gbps_fused']:8.1f} {r['keep']}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--e2e-iters", type=int, default=5)
+    ap.add_argument("--skip-layers", action="store_true")
+    ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_mobilenet: no GPU (timings are only meaningful on the device)")
+    dev = torch.device("cuda:0")
+    B = args.batch
+    layers = []
+    if not args.skip_layers:
+        pw, dw = layer_shapes(224)
+        for (H, C, K, act, res) in pw:
+            rec = bench_pointwise(B, H, C, K, act, res, dev, args.iters, args.rounds)
+            layers.append(rec)
+            print(json.dumps(rec), flush=True)
+        for (H, C, st) in dw:
+            rec = bench_depthwise(B, H, C, st, dev, args.iters, args.rounds)
+            layers.append(rec)
+            print(json.dumps(rec), flush=True)
+        _table(layers)
+    e2e = {} if args.skip_e2e else bench_end_to_end(B, dev, args.e2e_iters, args.rounds)
+    for name, r in e2e.items():
+        print(f"{name:10s} fused {r['ms_fused']:.3f} ms ({r['img_s_fused']} img/s)  "
+              f"unfused {r['ms_unfused']:.3f} ms ({r['img_s_unfused']} img/s)  "
+              f"spread {r['spread_unfused']:.3f}  speedup {r['speedup']}")
+    report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers, **e2e}
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(report, indent=2))
+    summary = {"bench": "mobilenet_v2_frozen", "batch": B,
+               "layers_kept": sum(r["keep"] for r in layers),
+               "layers_total": len(layers),
+               "layers_lost": [r["shape"] for r in layers if not r["keep"]]}
+    for name, r in e2e.items():
+        summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
+                                           "img_s_unfused", "speedup")}
+    print(json.dumps(summary), flush=True)
+
+
+if __name__ == "__main__":
+    main()

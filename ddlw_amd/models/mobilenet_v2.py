@@ -36,6 +36,7 @@ import torch.nn as nn
 from ..core.model_io import tag_model
 from ..ops.conv import Conv2d
 from ..ops.layers import BatchNormAct2d, GlobalAvgPool2d
+from ..ops import mbconv
 
 
 class InvertedResidual(nn.Module):
@@ -60,6 +61,9 @@ class InvertedResidual(nn.Module):
         self.conv = nn.Sequential(*layers)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if mbconv.inverted_residual_eval_fusable(self, x):
+            # frozen block: BN folded into the conv epilogues (ops/mbconv.py)
+            return mbconv.inverted_residual_eval_forward(self, x)
         return x + self.conv(x) if self.use_res else self.conv(x)
 
 
@@ -104,6 +108,17 @@ class MobileNetV2(nn.Module):
                 nn.init.zeros_(m.bias)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        n = len(self.features)
+        tail_conv, tail_bn = self.features[n - 3], self.features[n - 2]
+        if (mbconv.eval_fold_enabled(self, x)
+                and tail_bn.running_mean.dtype == torch.float32):
+            # frozen forward: the blocks fuse themselves; the 320->1280 tail
+            # conv + BN + ReLU6 is one pointwise kernel as well
+            for m in self.features[: n - 3]:
+                x = m(x)
+            return mbconv.conv_bn_eval(
+                tail_conv, tail_bn,
+                x.contiguous(memory_format=torch.channels_last))
         return self.features(x)
 
 

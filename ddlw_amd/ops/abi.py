@@ -66,6 +66,9 @@ SIGNATURES = {
     "ddlw_depthwise_dgrad": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_depthwise_wgrad_nparts": (_I, [_L, _I]),
     "ddlw_depthwise_wgrad": (_I, [_P, _P, _P, _P] + [_I] * 10 + [_P]),
+    # pointwise.hip
+    "ddlw_pw_conv_fwd": (_I, [_P] * 7 + [_I, _L, _I, _I, _P]),
+    "ddlw_depthwise_fwd_ep": (_I, [_P] * 5 + [_I] * 9 + [_P]),
     # conv_gemm.hip
     "ddlw_conv_fwd_nparts": (_L, [_I] * 8),
     "ddlw_conv_fwd_igemm": (_I, [_P] * 13 + [_I] * 15 + [_P]),

@@ -230,6 +230,81 @@ def depthwise_fwd(x: torch.Tensor, weight: torch.Tensor, stride: int, padding: i
     return y
 
 
+def _f32c(t: torch.Tensor, c: int) -> torch.Tensor:
+    """A contiguous fp32 per-channel vector of length ``c``, checked."""
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == c
+    return t
+
+
+def depthwise_fwd_ep(x: torch.Tensor, weight: torch.Tensor, scale: torch.Tensor,
+                     bias: torch.Tensor, act: int, stride: int,
+                     padding: int) -> torch.Tensor:
+    """Depthwise 3x3 forward with the folded-BN epilogue:
+    ``act(dw(x) * scale[c] + bias[c])``, act 0 none / 1 ReLU / 2 ReLU6.
+    scale and bias fp32 [C]; weight [C,1,3,3]."""
+    n, c, h, w = x.shape
+    _, _, r, s = weight.shape
+    assert (r, s) == (3, 3), "depthwise_fwd_ep is 3x3 only"
+    ho = (h + 2 * padding - r) // stride + 1
+    wo = (w + 2 * padding - s) // stride + 1
+    y = torch.empty((n, c, ho, wo), dtype=torch.bfloat16, device=x.device,
+                    memory_format=torch.channels_last)
+    launch("depthwise_fwd_ep", _nhwc(x), _depthwise_w_t(weight), _nhwc(y),
+           _f32c(scale, c), _f32c(bias, c), int(act), n, h, w, c, ho, wo,
+           stride, padding)
+    return y
+
+
+def pw_conv_supported(C: int, K: int) -> bool:
+    """Shapes ``pw_conv_fwd`` takes: 16-byte bf16x8 vectors on both channel
+    axes. No measured-loser exclusion: every pointwise shape of MobileNetV2
+    @224 beat the unfused path by more than its spread
+    (bench/bench_mobilenet.py; table and rule in docs/KERNELS.md)."""
+    return C > 0 and K > 0 and C % 8 == 0 and K % 8 == 0
+
+
+def pw_conv_fwd(x: torch.Tensor, weight: torch.Tensor,
+                scale: Optional[torch.Tensor] = None,
+                bias: Optional[torch.Tensor] = None, act: int = 0,
+                res: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """1x1 stride-1 conv on the MFMA pointwise kernel with its epilogue:
+    ``act(conv(x) * scale[k] + bias[k] + res)``. x channels_last bf16
+    [N,C,H,W] (or rows [M,C]); weight [K,C,1,1] (or [K,C]); scale/bias fp32
+    [K], both or neither; res like the output; act 0 none / 1 ReLU / 2 ReLU6.
+    ``out``: write into this bf16 tensor of the output's shape and layout."""
+    K, C = weight.shape[0], weight.shape[1]
+    rows, cx = _rows_c(x)
+    assert cx == C, f"pw_conv_fwd: x has {cx} channels, weight {C}"
+    if not pw_conv_supported(C, K):
+        raise ValueError(f"pw_conv_fwd: C={C}, K={K} must be multiples of 8")
+    w2 = weight.detach().reshape(K, C)
+    if w2.dtype != torch.bfloat16:
+        w2 = w2.to(torch.bfloat16)
+    w2 = w2.contiguous()
+    if x.dim() == 4:
+        n, _, h, w_ = x.shape
+        shape = (n, K, h, w_)
+    else:
+        shape = (rows, K)
+    if out is not None:
+        assert tuple(out.shape) == shape, "pw_conv_fwd: out has the wrong shape"
+        y = _nhwc(out)
+    elif x.dim() == 4:
+        y = torch.empty(shape, dtype=torch.bfloat16, device=x.device,
+                        memory_format=torch.channels_last)
+    else:
+        y = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+    if res is not None:
+        assert res.shape == y.shape, "pw_conv_fwd: res must match the output"
+        res = _nhwc(res)
+    if scale is not None:
+        scale, bias = _f32c(scale, K), _f32c(bias, K)
+    launch("pw_conv_fwd", _nhwc(x), w2, y, None, res, scale, bias, int(act),
+           rows, C, K)
+    return y
+
+
 def depthwise_dgrad(dy: torch.Tensor, weight: torch.Tensor, in_shape,
                     stride: int, padding: int) -> torch.Tensor:
     """Depthwise 3x3 conv2d input gradient. dy [N,C,Ho,Wo] channels_last

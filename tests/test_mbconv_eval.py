@@ -1,0 +1,453 @@
+"""Frozen MobileNetV2 on fused kernels: the pointwise MFMA conv and the
+depthwise forward with the folded-BN epilogue (``ops/hip/pointwise.hip``),
+their block-level composition (``ops/mbconv.py``) and the model wiring.
+
+Tolerance of the kernel parity tests: inputs are exact in bf16 and both
+kernels accumulate in fp32, so the only rounding of note is the output's
+(2^-8 relative); ``max|y - ref| <= 1e-2 * max|ref|`` leaves ~2.5x headroom.
+"""
+import copy
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from ddlw_amd.models.mobilenet_v2 import InvertedResidual, MobileNetV2, build_model
+from ddlw_amd.ops import mbconv
+
+TOL = 1e-2
+ENV_SWITCHES = ("DDLW_DISABLE_HIP_OPS", "DDLW_EVAL_FOLD", "DDLW_CONV")
+
+
+def _dev():
+    return torch.device("cuda:0")
+
+
+def _clear_env(monkeypatch):
+    for k in ENV_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+
+
+def _act(v, act):
+    return {0: lambda t: t, 1: F.relu, 2: F.relu6}[act](v)
+
+
+def _assert_regions(pre, what):
+    """Each region of the fp32 pre-activation holds >= 5% of the elements."""
+    n = pre.numel()
+    for name, cnt in (("<0", (pre < 0).sum()), ("(0,6)", ((pre > 0) & (pre < 6)).sum()),
+                      (">6", (pre > 6).sum())):
+        share = cnt.item() / n
+        print(f"{what} region {name}: {share:.3f}")
+        assert share >= 0.05, (what, name, share)
+
+
+def _check(y, ref, what):
+    assert torch.isfinite(y).all(), what
+    err = (y.float() - ref).abs().max().item()
+    bound = TOL * ref.abs().max().item()
+    print(f"{what}: max|y-ref| {err:.4e}  bound {bound:.4e}")
+    assert err <= bound, (what, err, bound)
+
+
+# --------------------------------------------------------------------------- #
+# 1. pointwise parity
+# --------------------------------------------------------------------------- #
+
+# (C, K, M): every C in {8,16,24,40,96,144,160,320}, K in {8,24,136,1280} and
+# M in {1, 147, 130, 162} at least once
+PW_SHAPES = [
+    (8, 8, 1), (16, 24, 147), (24, 136, 130), (40, 1280, 2 * 9 * 9),
+    (96, 24, 147), (144, 24, 130), (160, 136, 2 * 9 * 9), (320, 1280, 130),
+    (24, 8, 1), (16, 136, 147), (320, 24, 2 * 9 * 9), (96, 1280, 1),
+    # the other channels-per-wave instantiations of the kernel (64, 96, 192
+    # output channels per tile), the last with two tiles and a K tail
+    (32, 64, 147), (24, 96, 130), (64, 192, 2 * 9 * 9), (40, 376, 130),
+]
+# (name, scale/bias?, act, res?)
+PW_EPILOGUES = [("plain", False, 0, False), ("affine", True, 0, False),
+                ("relu", True, 1, False), ("relu6", True, 2, False),
+                ("res", True, 0, True)]
+
+
+def _pw_inputs(C, K, M, affine, res, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    dev = _dev()
+    x = torch.randn(M, C, generator=g).to(torch.bfloat16).to(dev)
+    w = torch.randn(K, C, generator=g).to(torch.bfloat16).to(dev)
+    scale = bias = r = None
+    if affine and M * K >= 1000:
+        # conv output ~ N(0, C): scale ~3/sqrt(C), bias ~3 puts the
+        # pre-activation at ~N(3, 3^2): ~16% < 0, ~68% in (0, 6), ~16% > 6
+        scale = (torch.empty(K).uniform_(0.9, 1.1, generator=g) * 3.0 / C ** 0.5).to(dev)
+        bias = torch.empty(K).uniform_(2.8, 3.2, generator=g).to(dev)
+    elif affine:
+        # too few elements to leave the regions to chance: pre-activation
+        # ~N(b, 0.3^2) with b cycling over the channels through -2, 3, 8
+        scale = (torch.empty(K).uniform_(0.9, 1.1, generator=g) * 0.3 / C ** 0.5).to(dev)
+        bias = torch.tensor([-2.0, 3.0, 8.0]).repeat(K // 3 + 1)[:K].to(dev)
+    if res:
+        r = torch.randn(M, K, generator=g).to(torch.bfloat16).to(dev)
+    return x, w, scale, bias, r
+
+
+def _pw_ref(x, w, scale, bias, r):
+    pre = x.float() @ w.float().T
+    if scale is not None:
+        pre = pre * scale + bias
+    if r is not None:
+        pre = pre + r.float()
+    return pre
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ep", PW_EPILOGUES, ids=[e[0] for e in PW_EPILOGUES])
+@pytest.mark.parametrize("shape", PW_SHAPES, ids=lambda s: "c%d_k%d_m%d" % s)
+def test_pw_conv_parity(shape, ep):
+    from ddlw_amd.ops import binding
+
+    C, K, M = shape
+    name, affine, act, res = ep
+    x, w, scale, bias, r = _pw_inputs(C, K, M, affine, res, seed=C * 7 + K + M)
+    pre = _pw_ref(x, w, scale, bias, r)
+    what = f"pw {shape} {name}"
+    y = binding.pw_conv_fwd(x, w.view(K, C, 1, 1), scale, bias, act, r)
+    assert y.shape == (M, K) and y.dtype == torch.bfloat16
+    _check(y, _act(pre, act), what)
+    if act == 2:
+        _assert_regions(pre, what)
+        assert y.max().item() == 6.0 and y.min().item() == 0.0
+
+
+@pytest.mark.gpu
+def test_pw_conv_nhwc_input_matches_rows():
+    """The 4-D channels_last entry is the same GEMM over N*H*W rows."""
+    from ddlw_amd.ops import binding
+
+    x, w, scale, bias, _ = _pw_inputs(24, 136, 3 * 7 * 7, True, False, seed=3)
+    x4 = x.view(3, 7, 7, 24).permute(0, 3, 1, 2)
+    y4 = binding.pw_conv_fwd(x4, w.view(136, 24, 1, 1), scale, bias, 2)
+    assert y4.shape == (3, 136, 7, 7)
+    assert y4.is_contiguous(memory_format=torch.channels_last)
+    y2 = binding.pw_conv_fwd(x, w, scale, bias, 2)
+    assert torch.equal(y4.permute(0, 2, 3, 1).reshape(-1, 136), y2)
+
+
+@pytest.mark.gpu
+def test_pw_conv_rejects_unsupported():
+    from ddlw_amd.ops import binding
+
+    assert binding.pw_conv_supported(24, 144)
+    assert not binding.pw_conv_supported(3, 32)
+    assert not binding.pw_conv_supported(32, 20)
+    x = torch.zeros(4, 12, dtype=torch.bfloat16, device=_dev())
+    w = torch.zeros(8, 12, dtype=torch.bfloat16, device=_dev())
+    with pytest.raises(ValueError):
+        binding.pw_conv_fwd(x, w)
+
+
+# --------------------------------------------------------------------------- #
+# 2. tails do not leak
+# --------------------------------------------------------------------------- #
+
+
+@pytest.mark.gpu
+def test_pw_conv_tails_do_not_leak():
+    """C=24 leaves an 8-channel tail in the 32-deep step, K=24 a K tail,
+    M=147 an M tail. x, w, res and y are row slices out of the middle of
+    larger buffers: NaN around the inputs must not reach the result and the
+    sentinels around y must survive."""
+    from ddlw_amd.ops import binding
+
+    C = K = 24
+    M, PAD = 147, 40
+    x, w, scale, bias, r = _pw_inputs(C, K, M, True, True, seed=5)
+    dev = _dev()
+
+    def embed(t, pad, fill):
+        buf = torch.full((t.shape[0] + 2 * pad, t.shape[1]), fill,
+                         dtype=torch.bfloat16, device=dev)
+        buf[pad:pad + t.shape[0]] = t
+        return buf, buf[pad:pad + t.shape[0]]
+
+    _, xs = embed(x, PAD, float("nan"))
+    _, ws = embed(w, 8, float("nan"))
+    _, rs = embed(r, PAD, float("nan"))
+    ybuf = torch.full((M + 2 * PAD, K), -1234.0, dtype=torch.bfloat16, device=dev)
+    before = ybuf.clone()
+    y = binding.pw_conv_fwd(xs, ws, scale, bias, 0, rs, out=ybuf[PAD:PAD + M])
+    assert y.data_ptr() == ybuf[PAD].data_ptr()
+    _check(y, _pw_ref(x, w, scale, bias, r), "pw tails")
+    assert torch.equal(ybuf[:PAD], before[:PAD])
+    assert torch.equal(ybuf[PAD + M:], before[PAD + M:])
+
+
+# --------------------------------------------------------------------------- #
+# 3. depthwise epilogue parity
+# --------------------------------------------------------------------------- #
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("act", [0, 2])
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("C", [8, 24, 144])
+def test_depthwise_fwd_ep_parity(C, stride, act):
+    from ddlw_amd.ops import binding
+
+    dev = _dev()
+    g = torch.Generator(device="cpu").manual_seed(100 + C + stride)
+    x = torch.randn(2, C, 5, 7, generator=g).to(torch.bfloat16).to(dev)
+    x = x.contiguous(memory_format=torch.channels_last)
+    w = torch.randn(C, 1, 3, 3, generator=g).to(torch.bfloat16).to(dev)
+    # 9 taps of N(0,1) products ~ N(0, 3^2) (less at the padded border)
+    scale = torch.empty(C).uniform_(0.9, 1.1, generator=g).to(dev)
+    bias = torch.empty(C).uniform_(2.8, 3.2, generator=g).to(dev)
+    pre = F.conv2d(x.float(), w.float(), stride=stride, padding=1, groups=C)
+    pre = pre * scale.view(1, C, 1, 1) + bias.view(1, C, 1, 1)
+    what = f"dw c{C} s{stride} act{act}"
+    y = binding.depthwise_fwd_ep(x, w, scale, bias, act, stride, 1)
+    assert y.shape == pre.shape
+    assert y.is_contiguous(memory_format=torch.channels_last)
+    _check(y, _act(pre, act), what)
+    if act == 2:
+        _assert_regions(pre, what)
+        assert y.max().item() == 6.0 and y.min().item() == 0.0
+
+
+# --------------------------------------------------------------------------- #
+# 4. block parity and routing
+# --------------------------------------------------------------------------- #
+
+
+def _randomize_bn(module, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    with torch.no_grad():
+        for mod in module.modules():
+            if isinstance(getattr(mod, "running_mean", None), torch.Tensor):
+                mod.running_mean.copy_(torch.empty_like(mod.running_mean, device="cpu").uniform_(-0.3, 0.3, generator=g))
+                mod.running_var.copy_(torch.empty_like(mod.running_var, device="cpu").uniform_(0.5, 1.5, generator=g))
+                mod.weight.copy_(torch.empty_like(mod.weight, device="cpu").uniform_(0.5, 1.5, generator=g))
+                mod.bias.copy_(torch.empty_like(mod.bias, device="cpu").uniform_(-0.2, 0.2, generator=g))
+
+
+def _to_bf16_convs(m):
+    m = copy.deepcopy(m).to(memory_format=torch.channels_last)
+    for mod in m.modules():
+        if isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear)):
+            mod.to(torch.bfloat16)
+    return m
+
+
+def _count_calls(monkeypatch, names=("pw_conv_fwd", "depthwise_fwd_ep", "bn_apply")):
+    from ddlw_amd.ops import binding
+
+    calls = {n: 0 for n in names}
+    for n in names:
+        real = getattr(binding, n)
+
+        def counted(*a, _real=real, _n=n, **k):
+            calls[_n] += 1
+            return _real(*a, **k)
+
+        monkeypatch.setattr(binding, n, counted)
+    return calls
+
+
+def _rel_l2(y, ref):
+    return ((y.float() - ref).norm() / (ref.norm() + 1e-30)).item()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", [(32, 16, 1, 1), (16, 24, 2, 6), (24, 24, 1, 6),
+                                 (160, 320, 1, 6)],
+                         ids=lambda c: "%dto%d_s%d_t%d" % c)
+def test_inverted_residual_block_parity_and_routing(cfg, monkeypatch):
+    """err(fused) <= 2*err(unfused) + 1e-3 in relative L2 against fp32 stock
+    ops: the parent path (DDLW_EVAL_FOLD=0) is the yardstick, 2x covers two
+    bf16 pipelines that round at different points."""
+    _clear_env(monkeypatch)
+    in_ch, out_ch, stride, t = cfg
+    dev = _dev()
+    torch.manual_seed(21)
+    blk32 = InvertedResidual(in_ch, out_ch, stride, t)
+    _randomize_bn(blk32, seed=in_ch + out_ch)
+    blk32 = blk32.to(dev).eval()
+    assert blk32.use_res == (cfg == (24, 24, 1, 6))
+    blk = _to_bf16_convs(blk32).eval()
+    x32 = torch.randn(2, in_ch, 9, 9, device=dev).to(torch.bfloat16).float()
+    x32 = x32.contiguous(memory_format=torch.channels_last)
+    xb = x32.to(torch.bfloat16)
+
+    calls = _count_calls(monkeypatch)
+    with torch.no_grad():
+        y_fused = blk(xb)
+        fused_calls = dict(calls)
+        for k in calls:
+            calls[k] = 0
+        monkeypatch.setenv("DDLW_EVAL_FOLD", "0")
+        y_unfused = blk(xb)
+        unfused_calls = dict(calls)
+        monkeypatch.delenv("DDLW_EVAL_FOLD")
+        monkeypatch.setenv("DDLW_DISABLE_HIP_OPS", "1")
+        y32 = blk32(x32)
+        monkeypatch.delenv("DDLW_DISABLE_HIP_OPS")
+
+    assert fused_calls == {"pw_conv_fwd": 1 if t == 1 else 2,
+                           "depthwise_fwd_ep": 1, "bn_apply": 0}, fused_calls
+    assert unfused_calls["pw_conv_fwd"] == 0 and unfused_calls["depthwise_fwd_ep"] == 0
+    assert unfused_calls["bn_apply"] == (2 if t == 1 else 3), unfused_calls
+    assert y_fused.shape == y32.shape and torch.isfinite(y_fused.float()).all()
+    e_f, e_u = _rel_l2(y_fused, y32), _rel_l2(y_unfused, y32)
+    print(f"block {cfg}: err_fused {e_f:.4e}  err_unfused {e_u:.4e}")
+    assert e_f <= 2 * e_u + 1e-3, (e_f, e_u)
+
+
+# --------------------------------------------------------------------------- #
+# 5. whole model
+# --------------------------------------------------------------------------- #
+
+
+@pytest.mark.gpu
+def test_frozen_model_head_training_on_fused_base(monkeypatch):
+    from ddlw_amd.ops.layers import softmax_cross_entropy
+
+    _clear_env(monkeypatch)
+    dev = _dev()
+    torch.manual_seed(31)
+    model = build_model(64, 64, 3, 5, dropout=0.0)
+    _randomize_bn(model, seed=9)
+    m = _to_bf16_convs(model.to(dev)).train()
+    assert not m.base.base.training
+    x = torch.randn(8, 3, 64, 64, device=dev).to(torch.bfloat16)
+    x = x.contiguous(memory_format=torch.channels_last)
+    labels = torch.randint(0, 5, (8,), device=dev)
+
+    calls = _count_calls(monkeypatch)
+    logits = m(x)
+    assert calls["bn_apply"] == 1, calls          # the 3->32 stem only
+    assert calls["pw_conv_fwd"] == 16 * 2 + 1 + 1  # 16 expanded, t=1, tail
+    assert calls["depthwise_fwd_ep"] == 17
+    loss = softmax_cross_entropy(logits, labels)
+    loss.backward()
+    assert m.classifier.weight.grad is not None
+    assert torch.isfinite(m.classifier.weight.grad.float()).all()
+    assert m.classifier.weight.grad.float().abs().max().item() > 0
+
+    monkeypatch.setenv("DDLW_EVAL_FOLD", "0")
+    for k in calls:
+        calls[k] = 0
+    with torch.no_grad():
+        ref = m(x)
+    assert calls["pw_conv_fwd"] == 0 and calls["depthwise_fwd_ep"] == 0
+    rel = ((logits.float() - ref.float()).abs().max() / (ref.float().abs().max() + 1e-6)).item()
+    print(f"frozen model logits: rel {rel:.4e}")
+    assert rel <= 5e-2, rel
+
+
+@pytest.mark.gpu
+def test_fine_tune_prefix_fused_suffix_trainable(monkeypatch):
+    from ddlw_amd.ops.layers import softmax_cross_entropy
+
+    _clear_env(monkeypatch)
+    dev = _dev()
+    torch.manual_seed(32)
+    model = build_model(64, 64, 3, 5, dropout=0.0, fine_tune_at=13)
+    m = _to_bf16_convs(model.to(dev)).train()
+    x = torch.randn(8, 3, 64, 64, device=dev).to(torch.bfloat16)
+    x = x.contiguous(memory_format=torch.channels_last)
+    labels = torch.randint(0, 5, (8,), device=dev)
+    calls = _count_calls(monkeypatch)
+    loss = softmax_cross_entropy(m(x), labels)
+    # frozen prefix features[3:13]: one t=1 block and nine expanded blocks
+    assert calls["pw_conv_fwd"] == 1 + 9 * 2, calls
+    assert calls["depthwise_fwd_ep"] == 10, calls
+    assert calls["bn_apply"] > 1, calls           # stem + the trainable suffix
+    loss.backward()
+    for name, p in m.base.base.features.named_parameters():
+        idx = int(name.split(".")[0])
+        assert (p.grad is not None) == (idx >= 13), name
+        if p.grad is not None:
+            assert torch.isfinite(p.grad.float()).all(), name
+
+
+# --------------------------------------------------------------------------- #
+# CPU: the gate, and unchanged behaviour off the fused route
+# --------------------------------------------------------------------------- #
+
+
+class _FakeCudaBf16:
+    """Stands in for a CUDA bf16 activation so the gate's other conditions
+    can be checked without a GPU."""
+    is_cuda = True
+    dtype = torch.bfloat16
+
+
+def test_fusable_gate(monkeypatch):
+    _clear_env(monkeypatch)
+    blk = InvertedResidual(16, 24, 2, 6).eval()
+    fake = _FakeCudaBf16()
+    with torch.no_grad():
+        assert mbconv.inverted_residual_eval_fusable(blk, fake)
+        assert not mbconv.inverted_residual_eval_fusable(blk, torch.randn(1, 16, 4, 4))
+        assert not mbconv.inverted_residual_eval_fusable(
+            blk, torch.randn(1, 16, 4, 4).to(torch.bfloat16))
+        blk.train()
+        assert not mbconv.inverted_residual_eval_fusable(blk, fake)
+        blk.eval()
+        for name, value in (("DDLW_DISABLE_HIP_OPS", "1"), ("DDLW_EVAL_FOLD", "0"),
+                            ("DDLW_CONV", "stock")):
+            monkeypatch.setenv(name, value)
+            assert not mbconv.inverted_residual_eval_fusable(blk, fake), name
+            monkeypatch.delenv(name)
+        assert mbconv.inverted_residual_eval_fusable(blk, fake)
+        blk.conv[1].running_mean = blk.conv[1].running_mean.to(torch.bfloat16)
+        assert not mbconv.inverted_residual_eval_fusable(blk, fake)
+    assert not mbconv.inverted_residual_eval_fusable(
+        InvertedResidual(16, 24, 2, 6).eval(), fake)  # grad enabled
+
+
+def test_cpu_forward_is_the_module_composition(monkeypatch):
+    _clear_env(monkeypatch)
+    torch.manual_seed(3)
+    x = torch.randn(2, 24, 9, 9)
+    for train in (False, True):
+        blk = InvertedResidual(24, 24, 1, 6).train(train)
+        _randomize_bn(blk, seed=1)
+        ref = copy.deepcopy(blk)
+        with torch.no_grad():
+            assert torch.equal(blk(x), x + ref.conv(x))
+    blk = InvertedResidual(24, 32, 2, 6).eval()
+    assert torch.equal(blk(x), blk.conv(x))
+
+    net = MobileNetV2().eval()
+    _randomize_bn(net, seed=2)
+    img = torch.randn(2, 3, 64, 64)
+    with torch.no_grad():
+        h = img
+        for child in net.features:
+            h = child(h)
+        assert torch.equal(net(img), h)
+
+    model = build_model(64, 64, 3, 5, dropout=0.0).eval()
+    with torch.no_grad():
+        h = img
+        for child in model.base.base.features:
+            h = child(h)
+        h = model.classifier(model.global_average_pooling(h))
+        assert torch.equal(model(img), h)
+
+
+def test_state_dict_keys_unchanged(monkeypatch):
+    """Same key list as the same module tree built with the fusion off, and
+    the layout the saved models rely on."""
+    _clear_env(monkeypatch)
+    keys = list(build_model().state_dict())
+    monkeypatch.setenv("DDLW_EVAL_FOLD", "0")
+    assert keys == list(build_model().state_dict())
+    feats = build_model().base.base.features
+    assert len(feats) == 23
+    assert "base.base.features.0.weight" in keys
+    assert "base.base.features.3.conv.0.weight" in keys       # t=1: depthwise first
+    assert "base.base.features.4.conv.7.running_var" in keys  # project BN
+    assert "base.base.features.20.weight" in keys and "classifier.bias" in keys
+    assert not [k for k in keys if "fold" in k or "mbconv" in k]
