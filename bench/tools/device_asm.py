@@ -21,9 +21,11 @@ from ddlw_amd.ops.build import FLAGS, HIPCC  # noqa: E402
 def kernels(asm: str) -> dict:
     """{symbol: text} — body and descriptor of each kernel. ``__hip_cuid_``
     lines differ between two compiles of the same file; the function index in
-    local labels (.LBB<n>_, .Lfunc_end<n>) moves with instantiation order."""
+    local labels (.LBB<n>_, .Lfunc_end<n>) moves with instantiation order,
+    and with its digit count the padding in front of a label's comment."""
     asm = "\n".join(l for l in asm.splitlines() if "__hip_cuid_" not in l)
     asm = re.sub(r"(\.LBB|\bBB|\.Lfunc_end|\.Lfunc_begin)\d+", r"\1", asm)
+    asm = re.sub(r"[ \t]+;", " ;", asm)
     out = {}
     for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n.*?^\t\.end_amdhsa_kernel$",
                          asm, re.M | re.S):

@@ -38,10 +38,10 @@ _P, _I, _L, _F = Ptr, c_int, c_long, c_float
 
 # name -> (restype, argtypes). Every launching export ends in ``void* stream``.
 SIGNATURES = {
-    # elementwise.hip
+    # core.hip
     "ddlw_last_error": (c_char_p, []),
     "ddlw_device_sync": (_I, []),
-    "ddlw_fused_adam": (_I, [_P, _I, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
+    # bn.hip
     "ddlw_bn_nparts": (_I, [_L, _I]),
     "ddlw_bn_stats": (_I, [_P, _P, _P, _L, _I, _P]),
     "ddlw_bn_parts_fold": (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
@@ -50,25 +50,29 @@ SIGNATURES = {
     "ddlw_bn_bwd_reduce": (_I, [_P] * 7 + [_L, _I, _I, _P]),
     "ddlw_bn_grad_finalize": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "ddlw_bn_bwd_dx": (_I, [_P] * 10 + [_L, _I, _I, _P]),
+    # pool.hip
     "ddlw_maxpool3x3s2_fwd": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),
     "ddlw_maxpool3x3s2_bwd": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),
     "ddlw_gap_fwd": (_I, [_P, _P, _I, _I, _I, _P]),
     "ddlw_gap_bwd": (_I, [_P, _P, _I, _I, _I, _P]),
+    # head.hip
     "ddlw_softmax_ce": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
-    "ddlw_fused_sgd": (_I, [_P, _I, _L, _F, _F, _F, _I, _P]),
-    "ddlw_normalize_u8": (_I, [_P, _P, _L, _P]),
-    "ddlw_depthwise_fwd": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_dropout_fwd": (_I, [_P, _P, _P, _L, _F, c_ulonglong, _P]),
     "ddlw_dropout_bwd": (_I, [_P, _P, _P, _L, _F, _P]),
     "ddlw_argmax_rows": (_I, [_P, _P, _L, _I, _P]),
     "ddlw_accuracy": (_I, [_P, _P, _P, _L, _I, _P]),
-    # depthwise_bwd.hip
+    "ddlw_normalize_u8": (_I, [_P, _P, _L, _P]),
+    # optim.hip
+    "ddlw_fused_sgd": (_I, [_P, _I, _L, _F, _F, _F, _I, _P]),
+    "ddlw_fused_adam": (_I, [_P, _I, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
+    # depthwise.hip
+    "ddlw_depthwise_fwd": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
+    "ddlw_depthwise_fwd_ep": (_I, [_P] * 5 + [_I] * 9 + [_P]),
     "ddlw_depthwise_dgrad": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_depthwise_wgrad_nparts": (_I, [_L, _I]),
     "ddlw_depthwise_wgrad": (_I, [_P, _P, _P, _P] + [_I] * 10 + [_P]),
     # pointwise.hip
-    "ddlw_pw_conv_fwd": (_I, [_P] * 7 + [_I, _L, _I, _I, _P]),
-    "ddlw_depthwise_fwd_ep": (_I, [_P] * 5 + [_I] * 9 + [_P]),
+    "ddlw_pw_conv_fwd": (_I, [_P] * 6 + [_I, _L, _I, _I, _P]),
     # conv_gemm.hip
     "ddlw_conv_fwd_nparts": (_L, [_I] * 8),
     "ddlw_conv_fwd_igemm": (_I, [_P] * 13 + [_I] * 15 + [_P]),

@@ -300,8 +300,8 @@ def pw_conv_fwd(x: torch.Tensor, weight: torch.Tensor,
         res = _nhwc(res)
     if scale is not None:
         scale, bias = _f32c(scale, K), _f32c(bias, K)
-    launch("pw_conv_fwd", _nhwc(x), w2, y, None, res, scale, bias, int(act),
-           rows, C, K)
+    launch("pw_conv_fwd", _nhwc(x), w2, y, res, scale, bias, int(act), rows, C,
+           K)
     return y
 
 

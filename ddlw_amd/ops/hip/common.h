@@ -45,8 +45,39 @@ __device__ __forceinline__ float warp_reduce_max(float v) {
   return v;
 }
 
-// error plumbing ------------------------------------------------------------
-#define DDLW_CHECK_LAUNCH()                                                    \
+// 8 consecutive fp32 (a per-channel table slice) as two 16-byte loads
+__device__ __forceinline__ void load8f(const float* __restrict__ p, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p);
+  const float4 b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// fused activation epilogue: 0 none, 1 ReLU, 2 ReLU6
+__device__ __forceinline__ float apply_act(float v, int act) {
+  if (act >= 1) v = fmaxf(v, 0.f);
+  if (act == 2) v = fminf(v, 6.f);
+  return v;
+}
+
+// Conv tap index clamped into [0, hi]: an out-of-range tap loads from this
+// (always valid) address and the loaded vector is zeroed afterwards, so the
+// tap loads of a pixel issue back to back with no branch between them.
+__device__ __forceinline__ int clamp_tap(int v, int hi) {
+  return v < 0 ? 0 : (v > hi ? hi : v);
+}
+
+// launch geometry -----------------------------------------------------------
+static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+
+// 1-D grid for a grid-stride kernel: ceil(work / block), at least 1, capped
+static inline int grid_1d(long work, int block = 256, int cap = 2048) {
+  long g = cdiv(work, block);
+  return (int)(g < cap ? (g > 0 ? g : 1) : cap);
+}
+
+// error plumbing (core.hip) -------------------------------------------------
+#define DDLW_CHECK_LAUNCH()                                                   \
   do {                                                                         \
     hipError_t err_ = hipGetLastError();                                       \
     if (err_ != hipSuccess) {                                                  \
@@ -57,6 +88,8 @@ __device__ __forceinline__ float warp_reduce_max(float v) {
   } while (0)
 
 void ddlw_set_error(const char* msg);
+// sets the error to "who: why" and returns 2 (the bad-argument status)
+int ddlw_fail(const char* who, const char* why);
 
 // launch dispatch -----------------------------------------------------------
 // Runtime value -> template argument: f is a generic lambda that receives a

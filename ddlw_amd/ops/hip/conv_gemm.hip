@@ -23,33 +23,13 @@
 //   - 2x2 wave grid, each wave (BM/2 x BN/2) of 16x16 fragments,
 //     v_mfma_f32_16x16x32_bf16, two K-halves per BK=64 step;
 //   - XCD-aware bijective workgroup swizzle (L2 tile locality).
-#include "common.h"
+#include "igemm.h"
 #include <cstdlib>
 #include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_v;
 typedef __attribute__((ext_vector_type(4))) float f32x4_v;
 typedef __attribute__((ext_vector_type(16))) float f32x16_v;
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
-
-// host-precomputed magic division (Granlund-Montgomery): q = (m*M) >> (64)
-// ... here the (32+s)-shift variant; valid for the m < 2^31 row indices.
-// Avoids the ~100-cycle 64-bit div/mod expansion per thread in the prologue
-// (dominant on 1-k-step shapes).
-__device__ __forceinline__ unsigned mdiv(unsigned m, unsigned long long magic,
-                                         unsigned shift) {
-  return (unsigned)(((unsigned long long)m * magic) >> shift);
-}
-
-// hardware RNE float->bf16 (v_cvt path; the integer-rounding f2b is ~5 VALU)
-__device__ __forceinline__ bf16_t f2b_hw(float f) {
-  __bf16 h = (__bf16)f;
-  union { __bf16 h; bf16_t u; } cvt;
-  cvt.h = h;
-  return cvt.u;
-}
 
 // BN-stats fusion: the conv epilogue already holds every output value in
 // registers — accumulating per-channel sum/sumsq here saves the separate
@@ -77,7 +57,7 @@ __device__ __forceinline__ void bn_partials_16(
         long m = tile_m * BM + (long)wr * WM + mi * 16 + d_row0 + qq;
         if (m < M) {
           union { unsigned i; float f; } cv;
-          cv.i = (unsigned)f2b_hw(acc[mi][ni][qq]) << 16;
+          cv.i = (unsigned)f2b(acc[mi][ni][qq]) << 16;
           s[ni] += cv.f;
           q[ni] += cv.f * cv.f;
         }
@@ -145,7 +125,7 @@ __device__ __forceinline__ void bnb_partials_16(
             v += ca.f;
           }
           union { unsigned i; float f; } cv;
-          cv.i = (unsigned)f2b_hw(v) << 16;  // the stored bf16 value
+          cv.i = (unsigned)f2b(v) << 16;  // the stored bf16 value
           bool on = true;
           if (bmask)
             on = (bmask[oi >> 3] >> (j & 7)) & 1;
@@ -473,7 +453,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
               long oi = out_row(m) * K + j;
               float v = acc2[mi][ni][reg];
               if (accp) v += b2f(accp[oi]);
-              y[oi] = f2b_hw(v);
+              y[oi] = f2b(v);
             }
           }
         }
@@ -503,7 +483,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
               if (ep_scale) v = v * eps_[ni] + epb_[ni];
               if (accp) v += b2f(accp[oi]);
               if (ep_relu) v = fmaxf(v, 0.f);
-              y[oi] = f2b_hw(v);
+              y[oi] = f2b(v);
             }
           }
         }
@@ -531,7 +511,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
         for (int reg = 0; reg < 16; ++reg) {
           int row = (reg & 3) + 8 * (reg >> 2) + d_rbase32;
           lC[(mi * 32 + row) * WNP + ni * 32 + d_col32] =
-              f2b_hw(acc2[mi][ni][reg]);
+              f2b(acc2[mi][ni][reg]);
         }
   } else {
     #pragma unroll
@@ -541,7 +521,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
         #pragma unroll
         for (int q = 0; q < 4; ++q)
           lC[(mi * 16 + d_row0 + q) * WNP + ni * 16 + d_col] =
-              f2b_hw(acc[mi][ni][q]);
+              f2b(acc[mi][ni][q]);
   }
   // wave-private region: lgkmcnt ordering suffices, no barrier needed
   constexpr int CPL = WN / 8;        // 16-B chunks per output row
@@ -563,7 +543,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
   auto ep_apply = [&](bf16_t v, int e, float accv) -> bf16_t {
     float f = b2f(v) * eps8[e] + epb8[e] + accv;
     if (ep_relu) f = fmaxf(f, 0.f);
-    return f2b_hw(f);
+    return f2b(f);
   };
   float s8[8], q8[8], bnm8[8], bnr8[8];
   #pragma unroll
@@ -607,8 +587,8 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
           // bf16+bf16 add numerics)
           uint4 a = *reinterpret_cast<const uint4*>(accp + orow * K + j_base);
           auto addpair = [&](unsigned v, unsigned aw) -> unsigned {
-            bf16_t lo = f2b_hw(b2f((bf16_t)(v & 0xffff)) + b2f((bf16_t)(aw & 0xffff)));
-            bf16_t hi = f2b_hw(b2f((bf16_t)(v >> 16)) + b2f((bf16_t)(aw >> 16)));
+            bf16_t lo = f2b(b2f((bf16_t)(v & 0xffff)) + b2f((bf16_t)(aw & 0xffff)));
+            bf16_t hi = f2b(b2f((bf16_t)(v >> 16)) + b2f((bf16_t)(aw >> 16)));
             return (unsigned)lo | ((unsigned)hi << 16);
           };
           val.x = addpair(val.x, a.x);
@@ -659,7 +639,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
               float av = accp ? b2f(accp[orow * K + j_base + e]) : 0.f;
               ov = ep_apply(ov, e, av);
             } else if (accp)
-              ov = f2b_hw(b2f(ov) + b2f(accp[orow * K + j_base + e]));
+              ov = f2b(b2f(ov) + b2f(accp[orow * K + j_base + e]));
             y[orow * K + j_base + e] = ov;
             if (bn_ps) {
               float f = b2f(ov);
@@ -944,7 +924,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_igemm_wide(
             long oi = out_row(m) * K + j;
             float v = acc[mi][ni][q];
             if constexpr (decltype(has_acc)::value) v += b2f(accp[oi]);
-            y[oi] = f2b_hw(v);
+            y[oi] = f2b(v);
           }
         }
       }
@@ -965,18 +945,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_igemm_wide(
 // ---------------------------------------------------------------------------
 // launcher: picks the tile instantiation by shape
 // ---------------------------------------------------------------------------
-static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
-
-// ceil-magic for q = m/d exact for all m < 2^31 (Granlund-Montgomery):
-// s = ceil(log2 d); magic = ceil(2^(32+s) / d); q = (m*magic) >> (32+s)
-static inline void make_magic(unsigned d, unsigned long long* magic, unsigned* shift) {
-  if (d == 1) { *magic = 1ull << 32; *shift = 32; return; }
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  *magic = ((1ull << (32 + s)) + d - 1) / d;
-  *shift = 32 + s;
-}
-
 struct TilePick {
   int bm, bn, bufs, wvm;
   bool epi_lds, wide, m32;

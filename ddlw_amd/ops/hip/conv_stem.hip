@@ -15,20 +15,12 @@
 // Tile: BM=128 x BN=64 (K=64), 4 waves (2x2), 2 LDS buffers, coalesced
 // LDS-bounce epilogue (short K-loop) — the same structure as the generic
 // kernel's short-K path.
-#include "common.h"
+#include "igemm.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 s_bf16x8_v;
 typedef __attribute__((ext_vector_type(4))) float s_f32x4_v;
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
-
 #define STEM_HALO 4
-
-__device__ __forceinline__ unsigned st_mdiv(unsigned m, unsigned long long magic,
-                                            unsigned shift) {
-  return (unsigned)(((unsigned long long)m * magic) >> shift);
-}
 
 // repack: bf16 NHWC C=3 -> [N][H][W+2*HALO][4] with zero c3 + zero halo
 __global__ __launch_bounds__(256) void k_stem_repack(
@@ -101,9 +93,9 @@ __global__ __launch_bounds__(256) void k_conv_stem(
     a_spair[p] = c8s & 3;    // pair of s taps (2 pixels = 16 B)
     if (m < M) {
       unsigned mu = (unsigned)m;
-      unsigned q1 = st_mdiv(mu, magic_wo, shift_wo);
+      unsigned q1 = mdiv(mu, magic_wo, shift_wo);
       int wo = (int)(mu - q1 * (unsigned)Wo);
-      unsigned n_u = st_mdiv(q1, magic_ho, shift_ho);
+      unsigned n_u = mdiv(q1, magic_ho, shift_ho);
       int ho = (int)(q1 - n_u * (unsigned)Ho);
       a_hb[p] = ho * stride - pad;  // input row of tap r=0
       // halo'd horizontal base: stored col = w + HALO, always >= 1
@@ -234,22 +226,11 @@ __global__ __launch_bounds__(256) void k_conv_stem(
   }
 }
 
-static inline long stem_cdiv(long a, long b) { return (a + b - 1) / b; }
-
-static inline void stem_magic(unsigned d, unsigned long long* magic,
-                              unsigned* shift) {
-  if (d == 1) { *magic = 1ull << 32; *shift = 32; return; }
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  *magic = ((1ull << (32 + s)) + d - 1) / d;
-  *shift = 32 + s;
-}
-
 DDLW_EXPORT int ddlw_stem_repack(const void* x, void* x4, int N, int H, int W,
                                  void* stream) {
   const int Wp = W + 2 * STEM_HALO;
   long npix = (long)N * H * Wp;
-  long grid = stem_cdiv(npix, 256);
+  long grid = cdiv(npix, 256);
   if (grid > 8192) grid = 8192;
   hipLaunchKernelGGL(k_stem_repack, dim3((int)grid), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)x4, npix,
@@ -270,9 +251,9 @@ DDLW_EXPORT int ddlw_conv_stem(const void* x4, const void* w4, void* y,
   long M = (long)N * Ho * Wo;
   unsigned long long mg_wo, mg_ho;
   unsigned sh_wo, sh_ho;
-  stem_magic((unsigned)Wo, &mg_wo, &sh_wo);
-  stem_magic((unsigned)Ho, &mg_ho, &sh_ho);
-  long grid = stem_cdiv(M, 128);
+  make_magic((unsigned)Wo, &mg_wo, &sh_wo);
+  make_magic((unsigned)Ho, &mg_ho, &sh_ho);
+  long grid = cdiv(M, 128);
   hipLaunchKernelGGL(k_conv_stem, dim3((int)grid), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)x4,
                      (const bf16_t*)w4, (bf16_t*)y, (const bf16_t*)zpage, N,
@@ -293,8 +274,6 @@ DDLW_EXPORT int ddlw_conv_stem(const void* x4, const void* w4, void* y,
 // real taps out of the padded result.
 // ---------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(2))) unsigned s_tr64_t;
-
-__global__ void k_wgrad_reduce(const float*, bf16_t*, long, int);
 
 __global__ __launch_bounds__(256) void k_stem_wgrad(
     const bf16_t* __restrict__ dy,   // [M][64]
@@ -344,9 +323,9 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(
       dyrow[g] = dv[g] ? (dy + m * K) : zpage;
       if (dv[g]) {
         unsigned mu = (unsigned)m;
-        unsigned q1 = st_mdiv(mu, magic_wo, shift_wo);
+        unsigned q1 = mdiv(mu, magic_wo, shift_wo);
         int wo = (int)(mu - q1 * (unsigned)Wo);
-        unsigned n_u = st_mdiv(q1, magic_ho, shift_ho);
+        unsigned n_u = mdiv(q1, magic_ho, shift_ho);
         int ho = (int)(q1 - n_u * (unsigned)Ho);
         xhb[g] = ho * stride - pad;
         xbase[g] = x4 + (((long)(int)n_u * H + xhb[g]) * Wp +
@@ -474,8 +453,8 @@ DDLW_EXPORT int ddlw_stem_wgrad(const void* dy, const void* x4,
   long M = (long)N * Ho * Wo;
   unsigned long long mg_wo, mg_ho;
   unsigned sh_wo, sh_ho;
-  stem_magic((unsigned)Wo, &mg_wo, &sh_wo);
-  stem_magic((unsigned)Ho, &mg_ho, &sh_ho);
+  make_magic((unsigned)Wo, &mg_wo, &sh_wo);
+  make_magic((unsigned)Ho, &mg_ho, &sh_ho);
   long m_per_split = (M + split - 1) / split;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_stem_wgrad, dim3(1, 1, split), dim3(256), 0, st,

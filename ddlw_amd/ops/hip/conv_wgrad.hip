@@ -25,19 +25,11 @@
 //     the even blocks, m 4-7 from the odd blocks), inline asm counted by an
 //     explicit lgkmcnt(0) + sched_barrier(0) before the MFMAs
 //     (cdna_hip_programming.md §5.4 rule 18, §5.7 form iii).
-#include "common.h"
+#include "igemm.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_v;
 typedef __attribute__((ext_vector_type(4))) float f32x4_v;
 typedef __attribute__((ext_vector_type(2))) unsigned tr64_t;
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
-
-__device__ __forceinline__ unsigned wg_mdiv(unsigned m, unsigned long long magic,
-                                            unsigned shift) {
-  return (unsigned)(((unsigned long long)m * magic) >> shift);
-}
 
 __device__ __forceinline__ unsigned lds_u32(const bf16_t* p) {
   return (unsigned)(unsigned long long)(const LDS_AS bf16_t*)p;
@@ -105,9 +97,9 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(
       const bf16_t* xr = zpage;
       if (m < m1) {
         unsigned mu = (unsigned)m;
-        unsigned q1 = wg_mdiv(mu, magic_wo, shift_wo);
+        unsigned q1 = mdiv(mu, magic_wo, shift_wo);
         int wo = (int)(mu - q1 * (unsigned)Wo);
-        unsigned n_u = wg_mdiv(q1, magic_ho, shift_ho);
+        unsigned n_u = mdiv(q1, magic_ho, shift_ho);
         int ho = (int)(q1 - n_u * (unsigned)Ho);
         int hh = ho * stride - pad + r;
         int wwv = wo * stride - pad + s;
@@ -250,16 +242,6 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(
   }
 }
 
-static inline long wg_cdiv(long a, long b) { return (a + b - 1) / b; }
-
-static inline void wg_magic(unsigned d, unsigned long long* magic, unsigned* shift) {
-  if (d == 1) { *magic = 1ull << 32; *shift = 32; return; }
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  *magic = ((1ull << (32 + s)) + d - 1) / d;
-  *shift = 32 + s;
-}
-
 DDLW_EXPORT int ddlw_conv_wgrad(const void* dy, const void* x, const void* zpage,
                                 void* slab, void* dw, int N, int H, int W_,
                                 int C, int K, int Ho, int Wo, int R, int S,
@@ -275,13 +257,13 @@ DDLW_EXPORT int ddlw_conv_wgrad(const void* dy, const void* x, const void* zpage
   }
   unsigned long long mg_wo, mg_ho;
   unsigned sh_wo, sh_ho;
-  wg_magic((unsigned)Wo, &mg_wo, &sh_wo);
-  wg_magic((unsigned)Ho, &mg_ho, &sh_ho);
-  long m_per_split = wg_cdiv(M, split);
+  make_magic((unsigned)Wo, &mg_wo, &sh_wo);
+  make_magic((unsigned)Ho, &mg_ho, &sh_ho);
+  long m_per_split = cdiv(M, split);
   hipStream_t st = (hipStream_t)stream;
 #define WLAUNCH3(BK, BC, BM_)                                                 \
   do {                                                                        \
-    dim3 grid((int)(wg_cdiv(K, BK) * wg_cdiv(C, BC)), R * S, split);          \
+    dim3 grid((int)(cdiv(K, BK) * cdiv(C, BC)), R * S, split);                \
     hipLaunchKernelGGL((k_conv_wgrad<BK, BC, BM_>), grid, dim3(256), 0, st,   \
                        (const bf16_t*)dy, (const bf16_t*)x,                   \
                        (const bf16_t*)zpage, (float*)slab, N, H, W_, C, K,    \
@@ -290,7 +272,7 @@ DDLW_EXPORT int ddlw_conv_wgrad(const void* dy, const void* x, const void* zpage
   } while (0)
 #define WLAUNCH(BK, BC)                                                       \
   do {                                                                        \
-    dim3 grid((int)(wg_cdiv(K, BK) * wg_cdiv(C, BC)), R * S, split);          \
+    dim3 grid((int)(cdiv(K, BK) * cdiv(C, BC)), R * S, split);                \
     hipLaunchKernelGGL((k_conv_wgrad<BK, BC>), grid, dim3(256), 0, st,        \
                        (const bf16_t*)dy, (const bf16_t*)x,                   \
                        (const bf16_t*)zpage, (float*)slab, N, H, W_, C, K,    \
@@ -313,7 +295,7 @@ DDLW_EXPORT int ddlw_conv_wgrad(const void* dy, const void* x, const void* zpage
     if (err_ != hipSuccess) { ddlw_set_error(hipGetErrorString(err_)); return 1; }
   }
   long elems = (long)K * R * S * C;
-  long g = wg_cdiv(elems, 32);
+  long g = cdiv(elems, 32);
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(k_wgrad_reduce, dim3((int)g), dim3(256), 0, st,
                      (const float*)slab, (bf16_t*)dw, elems, split);

@@ -1,25 +1,113 @@
-// Depthwise 3x3 conv2d backward (K2 — MobileNetV2's depthwise blocks), NHWC
-// bf16, fp32 accumulation, square stride 1 or 2, arbitrary pad, H != W ok.
-// Same data conventions as k_depthwise_fwd (elementwise.hip): C % 8 == 0,
-// 16-byte bf16x8 accesses, weights pre-transposed host-side to [R*S][C].
+// Depthwise conv2d (K2 — MobileNetV2's depthwise blocks), NHWC bf16, fp32
+// accumulation: training forward, eval forward with the folded-BN epilogue,
+// and the 3x3 backward (dgrad, wgrad + finalize).
+// Data conventions of the whole family: C % 8 == 0, 16-byte bf16x8 accesses,
+// weights pre-transposed host-side to [R*S][C] so the per-tap weight read is
+// the same contiguous vector shape as the activation read.
 //
-// Both directions are memory-bound. Out-of-range taps are handled by
-// loading from a CLAMPED (always valid) address and zeroing the vector
-// afterwards, so every tap load of a pixel is issued back to back with no
-// branch (and no wait) between them.
-#include "common.h"
-#include <cstdio>
+// Every direction is memory-bound. All kernels but k_depthwise_fwd handle
+// out-of-range taps by loading from a CLAMPED (always valid) address and
+// zeroing the vector afterwards (clamp_tap), so every tap load of a pixel is
+// issued back to back with no branch (and no wait) between them.
+#include "column.h"
 
-#define DW_K 3               // kernel extent (R == S == 3)
+#define DW_K 3               // kernel extent of the 3x3-only kernels
 #define DW_MAX_PARTS 512     // row-slice partials of the wgrad (2 blocks/CU)
 
-static inline int dw_grid_1d(long work) {
-  long b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+// ---------------------------------------------------------------------------
+// Training forward, any R x S and stride: one thread per 8-channel vector of
+// one output pixel, out-of-range taps skipped by a branch.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_depthwise_fwd(
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ w_t,
+    bf16_t* __restrict__ y, int N, int H, int W_, int C, int Ho, int Wo,
+    int R, int S, int stride, int pad) {
+  const int vecC = C >> 3;
+  const long total = (long)N * Ho * Wo * vecC;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    int vc = (int)(i % vecC);
+    long t = i / vecC;
+    int wo = (int)(t % Wo); t /= Wo;
+    int ho = (int)(t % Ho); t /= Ho;
+    int n = (int)t;
+    const int hb = ho * stride - pad, wb = wo * stride - pad;
+    float acc[8] = {0};
+    for (int r = 0; r < R; ++r) {
+      int h = hb + r;
+      if (h < 0 || h >= H) continue;
+      for (int s = 0; s < S; ++s) {
+        int ww = wb + s;
+        if (ww < 0 || ww >= W_) continue;
+        bf16x8 vx, vw;
+        vx.v = *reinterpret_cast<const uint4*>(
+            x + (((long)n * H + h) * W_ + ww) * C + (long)vc * 8);
+        vw.v = *reinterpret_cast<const uint4*>(
+            w_t + ((long)r * S + s) * C + (long)vc * 8);
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += b2f(vx.h[k]) * b2f(vw.h[k]);
+      }
+    }
+    bf16x8 o;
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) o.h[k] = f2b(acc[k]);
+    *reinterpret_cast<uint4*>(y + i * 8) = o.v;
+  }
 }
 
-__device__ __forceinline__ int dw_clamp(int v, int hi) {
-  return v < 0 ? 0 : (v > hi ? hi : v);
+// ---------------------------------------------------------------------------
+// Eval forward, 3x3, with the frozen model's folded-BN epilogue (the one
+// k_pw_conv applies): y = act(dw(x)*scale[c]+bias[c]), act 0 none, 1 ReLU,
+// 2 ReLU6. k_depthwise_fwd's thread mapping with clamped taps.
+// ---------------------------------------------------------------------------
+template <int STRIDE>
+__global__ __launch_bounds__(256) void k_depthwise_fwd_ep(
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ w_t,
+    bf16_t* __restrict__ y, const float* __restrict__ scale,
+    const float* __restrict__ bias, int act, int N, int H, int W_, int C,
+    int Ho, int Wo, int pad) {
+  const int vecC = C >> 3;
+  const long total = (long)N * Ho * Wo * vecC;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    const int vc = (int)(i % vecC);
+    long t = i / vecC;
+    const int wo = (int)(t % Wo); t /= Wo;
+    const int ho = (int)(t % Ho); t /= Ho;
+    const long n = t;
+    const int hb = ho * STRIDE - pad, wb = wo * STRIDE - pad;
+    float acc[8] = {0};
+    // one tap row (3 x + 3 w vectors) in flight at a time: with all nine taps
+    // unrolled the 18 live vectors cost 138 VGPRs = 3 waves/SIMD, and on
+    // this memory-bound kernel occupancy hides more latency than issue order
+    #pragma unroll 1
+    for (int r = 0; r < 3; ++r) {
+      const int h = hb + r;
+      const bool okr = (h >= 0) && (h < H);
+      const int hc = clamp_tap(h, H - 1);
+      #pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int ww = wb + s;
+        const bool ok = okr && (ww >= 0) && (ww < W_);
+        const int wc = clamp_tap(ww, W_ - 1);
+        bf16x8 vx, vw;
+        vx.v = *reinterpret_cast<const uint4*>(
+            x + ((n * H + hc) * W_ + wc) * C + (long)vc * 8);
+        vw.v = *reinterpret_cast<const uint4*>(
+            w_t + (long)(r * 3 + s) * C + (long)vc * 8);
+        if (!ok) vx.v = make_uint4(0u, 0u, 0u, 0u);
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += b2f(vx.h[k]) * b2f(vw.h[k]);
+      }
+    }
+    float sc[8], bi[8];
+    load8f(scale + vc * 8, sc);
+    load8f(bias + vc * 8, bi);
+    bf16x8 o;
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) o.h[k] = f2b(apply_act(acc[k] * sc[k] + bi[k], act));
+    *reinterpret_cast<uint4*>(y + i * 8) = o.v;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -54,14 +142,14 @@ __global__ __launch_bounds__(256) void k_depthwise_dgrad(
       const int r = r0 + a * STRIDE;
       const int ho = (hp - r) / STRIDE;        // exact by construction
       const bool okr = (r < DW_K) && (hp >= r) && (ho < Ho);
-      const int hoc = dw_clamp(ho, Ho - 1);
+      const int hoc = clamp_tap(ho, Ho - 1);
       const int rc = r < DW_K ? r : DW_K - 1;
       #pragma unroll
       for (int b = 0; b < TAPS; ++b) {
         const int s = s0 + b * STRIDE;
         const int wo = (wp - s) / STRIDE;
         const bool ok = okr && (s < DW_K) && (wp >= s) && (wo < Wo);
-        const int woc = dw_clamp(wo, Wo - 1);
+        const int woc = clamp_tap(wo, Wo - 1);
         const int sc = s < DW_K ? s : DW_K - 1;
         bf16x8 vd, vw;
         vd.v = *reinterpret_cast<const uint4*>(
@@ -83,9 +171,9 @@ __global__ __launch_bounds__(256) void k_depthwise_dgrad(
 // ---------------------------------------------------------------------------
 // wgrad: dw[c,r,s] = sum_{n,ho,wo} dy[n,ho,wo,c] * x[n,ho*st-pad+r,wo*st-pad+s,c]
 // A per-channel reduction over rows = N*Ho*Wo output pixels — the problem
-// shape of k_bn_bwd_reduce, and the same geometry: each thread owns ONE
-// fixed 8-channel vector column, thread groups stack over rows, grid.y
-// slices the rows. A thread keeps 9 taps x 8 channels of fp32 accumulators
+// shape of k_bn_bwd_reduce (bn.hip), and the same column geometry
+// (column.h): each thread owns ONE fixed 8-channel vector column, thread
+// groups stack over rows, grid.y slices the rows. A thread keeps 9 taps x 8 channels of fp32 accumulators
 // in registers (every index is compile-time: the tap loops are unrolled).
 // Row groups are summed through LDS in fixed order, one tap at a time, and
 // each block writes one [9][C] fp32 partial. No atomics: the result does
@@ -96,14 +184,11 @@ __global__ __launch_bounds__(256) void k_depthwise_wgrad_part(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
     float* __restrict__ part, int N, int H, int W_, int C, int Ho, int Wo,
     int pad) {
-  const int vecC = C >> 3;
-  const int VPB = vecC < 256 ? vecC : 256;      // vectors per block
-  const int ROWG = 256 / VPB;                   // row groups per block
-  const int tid = threadIdx.x;
-  const int vec = blockIdx.x * VPB + (tid % VPB);
-  const int rowg = tid / VPB;
+  const ColumnGeom cg(C);
+  const int ROWG = cg.ROWG;
+  const int vec = cg.vec(), rowg = cg.rowg();
   // inactive threads still reach every barrier (no early return)
-  const bool active = (rowg < ROWG) && (vec < vecC);
+  const bool active = cg.active();
 
   float acc[DW_K * DW_K][8];
   #pragma unroll
@@ -131,12 +216,12 @@ __global__ __launch_bounds__(256) void k_depthwise_wgrad_part(
       for (int r = 0; r < DW_K; ++r) {
         const int h = hb + r;
         const bool okr = (h >= 0) && (h < H);
-        const int hc = dw_clamp(h, H - 1);
+        const int hc = clamp_tap(h, H - 1);
         #pragma unroll
         for (int s = 0; s < DW_K; ++s) {
           const int w = wb + s;
           const bool ok = okr && (w >= 0) && (w < W_);
-          const int wc = dw_clamp(w, W_ - 1);
+          const int wc = clamp_tap(w, W_ - 1);
           vx[r * DW_K + s].v = *reinterpret_cast<const uint4*>(
               x + (long)((n * H + hc) * W_ + wc) * C + (long)vec * 8);
           if (!ok) vx[r * DW_K + s].v = make_uint4(0u, 0u, 0u, 0u);
@@ -157,15 +242,8 @@ __global__ __launch_bounds__(256) void k_depthwise_wgrad_part(
   #pragma unroll
   for (int t = 0; t < DW_K * DW_K; ++t) {
     if (ROWG > 1) {                             // block-uniform
-      #pragma unroll
-      for (int k = 0; k < 8; ++k) lds[tid * 8 + k] = acc[t][k];
-      __syncthreads();
-      if (rowg == 0)
-        for (int g = 1; g < ROWG; ++g)
-          #pragma unroll
-          for (int k = 0; k < 8; ++k)
-            acc[t][k] += lds[(g * VPB + (tid % VPB)) * 8 + k];
-      __syncthreads();
+      rowgroup_reduce8(cg, lds, acc[t]);
+      __syncthreads();                          // lds is reused by the next tap
     }
     if (active && rowg == 0) {
       float4* o = reinterpret_cast<float4*>(pout + (long)t * C);
@@ -206,7 +284,6 @@ __global__ __launch_bounds__(256) void k_depthwise_wgrad_finalize(
 // ---------------------------------------------------------------------------
 static int dw_check(const char* who, int C, int R, int S, int stride, int pad,
                     int H, int W_, int Ho, int Wo) {
-  static __thread char msg[160];
   const char* why = nullptr;
   if (C <= 0 || C % 8 != 0) why = "C must be a positive multiple of 8";
   else if (R != DW_K || S != DW_K) why = "kernel must be 3x3";
@@ -216,10 +293,45 @@ static int dw_check(const char* who, int C, int R, int S, int stride, int pad,
   else if (Ho != (H + 2 * pad - DW_K) / stride + 1 ||
            Wo != (W_ + 2 * pad - DW_K) / stride + 1)
     why = "output extent does not match input extent";
-  if (!why) return 0;
-  snprintf(msg, sizeof(msg), "%s: %s", who, why);
-  ddlw_set_error(msg);
-  return 2;
+  return why ? ddlw_fail(who, why) : 0;
+}
+
+DDLW_EXPORT int ddlw_depthwise_fwd(const void* x, const void* w_t, void* y,
+                                   int N, int H, int W_, int C, int Ho, int Wo,
+                                   int R, int S, int stride, int pad,
+                                   void* stream) {
+  if (C % 8 != 0) return ddlw_fail("depthwise_fwd", "C must be a multiple of 8");
+  long total = (long)N * Ho * Wo * (C >> 3);
+  hipLaunchKernelGGL(k_depthwise_fwd, dim3(grid_1d(total)), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w_t,
+                     (bf16_t*)y, N, H, W_, C, Ho, Wo, R, S, stride, pad);
+  DDLW_CHECK_LAUNCH();
+}
+
+DDLW_EXPORT int ddlw_depthwise_fwd_ep(const void* x, const void* w_t, void* y,
+                                      const void* scale, const void* bias,
+                                      int act, int N, int H, int W_, int C,
+                                      int Ho, int Wo, int stride, int pad,
+                                      void* stream) {
+  auto fail = [](const char* why) { return ddlw_fail("depthwise_fwd_ep", why); };
+  if (C <= 0 || C % 8 != 0) return fail("C must be a positive multiple of 8");
+  if (stride != 1 && stride != 2) return fail("stride must be 1 or 2");
+  if (pad < 0) return fail("pad must be >= 0");
+  if (act < 0 || act > 2) return fail("act must be 0, 1 or 2");
+  if (!scale || !bias) return fail("scale and bias are required");
+  if (N <= 0 || H <= 0 || W_ <= 0 || Ho <= 0 || Wo <= 0)
+    return fail("empty extent");
+  if (Ho != (H + 2 * pad - 3) / stride + 1 || Wo != (W_ + 2 * pad - 3) / stride + 1)
+    return fail("output extent does not match input extent");
+  const long total = (long)N * Ho * Wo * (C >> 3);
+  const int grid = grid_1d(total, 256, 4096);
+  with_int<1, 2>(stride, [&](auto ST) {
+    hipLaunchKernelGGL((k_depthwise_fwd_ep<decltype(ST)::value>), dim3(grid),
+                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       (const bf16_t*)w_t, (bf16_t*)y, (const float*)scale,
+                       (const float*)bias, act, N, H, W_, C, Ho, Wo, pad);
+  });
+  DDLW_CHECK_LAUNCH();
 }
 
 DDLW_EXPORT int ddlw_depthwise_dgrad(const void* dy, const void* w_t, void* dx,
@@ -230,31 +342,19 @@ DDLW_EXPORT int ddlw_depthwise_dgrad(const void* dy, const void* w_t, void* dx,
     return e;
   const long total = (long)N * H * W_ * (C >> 3);
   if (total <= 0) return 0;
-  if (stride == 1)
-    hipLaunchKernelGGL((k_depthwise_dgrad<1>), dim3(dw_grid_1d(total)),
-                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)w_t, (bf16_t*)dx, N, H, W_, C, Ho, Wo,
-                       pad);
-  else
-    hipLaunchKernelGGL((k_depthwise_dgrad<2>), dim3(dw_grid_1d(total)),
-                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)w_t, (bf16_t*)dx, N, H, W_, C, Ho, Wo,
-                       pad);
+  with_int<1, 2>(stride, [&](auto ST) {
+    hipLaunchKernelGGL((k_depthwise_dgrad<decltype(ST)::value>),
+                       dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)dy, (const bf16_t*)w_t, (bf16_t*)dx, N,
+                       H, W_, C, Ho, Wo, pad);
+  });
   DDLW_CHECK_LAUNCH();
 }
 
 // number of [9][C] row-slice partials the wgrad writes for `rows` = N*Ho*Wo
 DDLW_EXPORT int ddlw_depthwise_wgrad_nparts(long rows, int C) {
-  int vecC = C >> 3;
-  if (vecC < 1) return 1;
-  int VPB = vecC < 256 ? vecC : 256;
-  int ROWG = 256 / VPB;
-  int gx = (vecC + VPB - 1) / VPB;
-  long need = (rows + ROWG - 1) / ROWG;
-  long cap = DW_MAX_PARTS / gx;
-  if (cap < 1) cap = 1;
-  long ny = need < cap ? need : cap;
-  return (int)(ny < 1 ? 1 : ny);
+  if (C < 8) return 1;
+  return ColumnGeom(C).capped_slices(rows, DW_MAX_PARTS);
 }
 
 DDLW_EXPORT int ddlw_depthwise_wgrad(const void* dy, const void* x, void* part,
@@ -263,28 +363,18 @@ DDLW_EXPORT int ddlw_depthwise_wgrad(const void* dy, const void* x, void* part,
                                      int pad, void* stream) {
   if (int e = dw_check("depthwise_wgrad", C, R, S, stride, pad, H, W_, Ho, Wo))
     return e;
-  if (N <= 0) {
-    ddlw_set_error("depthwise_wgrad: empty batch");
-    return 2;
-  }
-  if ((long)N * H * W_ >= (1l << 30) || (long)N * Ho * Wo >= (1l << 30)) {
-    ddlw_set_error("depthwise_wgrad: tensor too large for 32-bit pixel indexing");
-    return 2;
-  }
-  const int vecC = C >> 3;
-  const int VPB = vecC < 256 ? vecC : 256;
+  if (N <= 0) return ddlw_fail("depthwise_wgrad", "empty batch");
+  if ((long)N * H * W_ >= (1l << 30) || (long)N * Ho * Wo >= (1l << 30))
+    return ddlw_fail("depthwise_wgrad",
+                     "tensor too large for 32-bit pixel indexing");
   const int nparts = ddlw_depthwise_wgrad_nparts((long)N * Ho * Wo, C);
-  dim3 grid((vecC + VPB - 1) / VPB, nparts);
-  if (stride == 1)
-    hipLaunchKernelGGL((k_depthwise_wgrad_part<1>), grid, dim3(256), 0,
-                       (hipStream_t)stream, (const bf16_t*)dy,
+  dim3 grid(ColumnGeom(C).gx, nparts);
+  with_int<1, 2>(stride, [&](auto ST) {
+    hipLaunchKernelGGL((k_depthwise_wgrad_part<decltype(ST)::value>), grid,
+                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)x, (float*)part, N, H, W_, C, Ho, Wo,
                        pad);
-  else
-    hipLaunchKernelGGL((k_depthwise_wgrad_part<2>), grid, dim3(256), 0,
-                       (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)x, (float*)part, N, H, W_, C, Ho, Wo,
-                       pad);
+  });
   hipLaunchKernelGGL(k_depthwise_wgrad_finalize,
                      dim3((C + 31) / 32, DW_K * DW_K), dim3(256), 0,
                      (hipStream_t)stream, (const float*)part, (float*)dw, C,

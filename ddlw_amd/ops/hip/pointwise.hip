@@ -1,5 +1,5 @@
-// Frozen-MobileNetV2 forward kernels: pointwise (1x1, stride 1, pad 0) conv on
-// MFMA and depthwise 3x3 forward, both with the folded-BN epilogue
+// Frozen-MobileNetV2 pointwise (1x1, stride 1, pad 0) conv on MFMA with the
+// folded-BN epilogue (k_depthwise_fwd_ep in depthwise.hip applies the same one)
 //   y = act(conv(x) * scale[k] + bias[k] (+ res)),   act: 0 none, 1 ReLU, 2 ReLU6
 // NHWC bf16 in/out, fp32 accumulation and epilogue, one rounding to bf16.
 //
@@ -28,7 +28,6 @@
 //     Consecutive blocks walk the N tiles of one row tile so the re-read of
 //     x comes from cache.
 #include "common.h"
-#include <cstdio>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 pw_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float pw_f32x4;
@@ -36,12 +35,6 @@ typedef __attribute__((ext_vector_type(4))) float pw_f32x4;
 #define PW_MR 2                    // 16-row fragments per wave
 #define PW_WAVES 4
 #define PW_BM (PW_WAVES * PW_MR * 16)
-
-__device__ __forceinline__ float pw_act(float v, int act) {
-  if (act >= 1) v = fmaxf(v, 0.f);
-  if (act == 2) v = fminf(v, 6.f);
-  return v;
-}
 
 template <int NP, bool HAS_RES>
 __global__ __launch_bounds__(256) void k_pw_conv(
@@ -121,14 +114,8 @@ __global__ __launch_bounds__(256) void k_pw_conv(
     if (kb >= K) continue;
     float sc[8], bi[8];
     if (scale) {
-      const float4 s0 = *reinterpret_cast<const float4*>(scale + kb);
-      const float4 s1 = *reinterpret_cast<const float4*>(scale + kb + 4);
-      const float4 b0 = *reinterpret_cast<const float4*>(bias + kb);
-      const float4 b1 = *reinterpret_cast<const float4*>(bias + kb + 4);
-      sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w;
-      sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
-      bi[0] = b0.x; bi[1] = b0.y; bi[2] = b0.z; bi[3] = b0.w;
-      bi[4] = b1.x; bi[5] = b1.y; bi[6] = b1.z; bi[7] = b1.w;
+      load8f(scale + kb, sc);
+      load8f(bias + kb, bi);
     } else {
       #pragma unroll
       for (int e = 0; e < 8; ++e) { sc[e] = 1.f; bi[e] = 0.f; }
@@ -150,17 +137,10 @@ __global__ __launch_bounds__(256) void k_pw_conv(
       }
       bf16x8 o;
       #pragma unroll
-      for (int e = 0; e < 8; ++e) o.h[e] = f2b(pw_act(v[e], act));
+      for (int e = 0; e < 8; ++e) o.h[e] = f2b(apply_act(v[e], act));
       *reinterpret_cast<uint4*>(y + oi) = o.v;
     }
   }
-}
-
-static int pw_fail(const char* why) {
-  static __thread char msg[160];
-  snprintf(msg, sizeof(msg), "pw_conv_fwd: %s", why);
-  ddlw_set_error(msg);
-  return 2;
 }
 
 // 32-channel fragment pairs per wave: the smallest listed NP that covers K in
@@ -175,27 +155,26 @@ static int pw_pick_np(int K) {
 }
 
 // x [M][C], w [K][C], y/res [M][K] bf16; scale/bias fp32 [K] (both or
-// neither). `zpage` is part of the ABI for an LDS-direct staging variant; the
-// kernel stages tails through predicated registers and does not read it.
+// neither).
 DDLW_EXPORT int ddlw_pw_conv_fwd(const void* x, const void* w, void* y,
-                                 const void* zpage, const void* res,
-                                 const void* scale, const void* bias, int act,
-                                 long M, int C, int K, void* stream) {
-  (void)zpage;
+                                 const void* res, const void* scale,
+                                 const void* bias, int act, long M, int C,
+                                 int K, void* stream) {
+  auto fail = [](const char* why) { return ddlw_fail("pw_conv_fwd", why); };
   if (C <= 0 || C % 8 != 0 || K <= 0 || K % 8 != 0)
-    return pw_fail("C and K must be positive multiples of 8");
-  if (M < 0 || M >= (1l << 31)) return pw_fail("M must be below 2^31");
-  if (act < 0 || act > 2) return pw_fail("act must be 0, 1 or 2");
+    return fail("C and K must be positive multiples of 8");
+  if (M < 0 || M >= (1l << 31)) return fail("M must be below 2^31");
+  if (act < 0 || act > 2) return fail("act must be 0, 1 or 2");
   if ((scale == nullptr) != (bias == nullptr))
-    return pw_fail("scale and bias come together");
+    return fail("scale and bias come together");
   if ((((size_t)x | (size_t)w | (size_t)y | (size_t)res | (size_t)scale |
         (size_t)bias) & 15) != 0)
-    return pw_fail("pointers must be 16-byte aligned");
+    return fail("pointers must be 16-byte aligned");
   if (M == 0) return 0;
   const int np = pw_pick_np(K);
   const int ntiles = (K + np * 32 - 1) / (np * 32);
-  const long blocks = (M + PW_BM - 1) / PW_BM * ntiles;
-  if (blocks >= (1l << 31)) return pw_fail("grid too large");
+  const long blocks = cdiv(M, PW_BM) * ntiles;
+  if (blocks >= (1l << 31)) return fail("grid too large");
   with_int<1, 2, 3, 5, 6>(np, [&](auto NPc) {
     with_bool(res != nullptr, [&](auto HR) {
       hipLaunchKernelGGL((k_pw_conv<decltype(NPc)::value, decltype(HR)::value>),
@@ -205,99 +184,6 @@ DDLW_EXPORT int ddlw_pw_conv_fwd(const void* x, const void* w, void* y,
                          (const float*)scale, (const float*)bias, act, M, C, K,
                          ntiles);
     });
-  });
-  DDLW_CHECK_LAUNCH();
-}
-
-// ---------------------------------------------------------------------------
-// Depthwise 3x3 forward with the same epilogue: y = act(dw(x)*scale[c]+bias[c]).
-// k_depthwise_fwd's thread mapping (one thread per 8-channel vector of one
-// output pixel) with the backward kernels' tap handling: out-of-range taps
-// load from a clamped valid address and are zeroed, so the loads of a tap
-// row issue back to back with no branch between them.
-// ---------------------------------------------------------------------------
-template <int STRIDE>
-__global__ __launch_bounds__(256) void k_depthwise_fwd_ep(
-    const bf16_t* __restrict__ x, const bf16_t* __restrict__ w_t,
-    bf16_t* __restrict__ y, const float* __restrict__ scale,
-    const float* __restrict__ bias, int act, int N, int H, int W_, int C,
-    int Ho, int Wo, int pad) {
-  const int vecC = C >> 3;
-  const long total = (long)N * Ho * Wo * vecC;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long)gridDim.x * blockDim.x) {
-    const int vc = (int)(i % vecC);
-    long t = i / vecC;
-    const int wo = (int)(t % Wo); t /= Wo;
-    const int ho = (int)(t % Ho); t /= Ho;
-    const long n = t;
-    const int hb = ho * STRIDE - pad, wb = wo * STRIDE - pad;
-    float acc[8] = {0};
-    // one tap row (3 x + 3 w vectors) in flight at a time: with all nine taps
-    // unrolled the 18 live vectors cost 138 VGPRs = 3 waves/SIMD, and on
-    // this memory-bound kernel occupancy hides more latency than issue order
-    #pragma unroll 1
-    for (int r = 0; r < 3; ++r) {
-      const int h = hb + r;
-      const bool okr = (h >= 0) && (h < H);
-      const int hc = h < 0 ? 0 : (h > H - 1 ? H - 1 : h);
-      #pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const int ww = wb + s;
-        const bool ok = okr && (ww >= 0) && (ww < W_);
-        const int wc = ww < 0 ? 0 : (ww > W_ - 1 ? W_ - 1 : ww);
-        bf16x8 vx, vw;
-        vx.v = *reinterpret_cast<const uint4*>(
-            x + ((n * H + hc) * W_ + wc) * C + (long)vc * 8);
-        vw.v = *reinterpret_cast<const uint4*>(
-            w_t + (long)(r * 3 + s) * C + (long)vc * 8);
-        if (!ok) vx.v = make_uint4(0u, 0u, 0u, 0u);
-        #pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] += b2f(vx.h[k]) * b2f(vw.h[k]);
-      }
-    }
-    const float4 s0 = *reinterpret_cast<const float4*>(scale + vc * 8);
-    const float4 s1 = *reinterpret_cast<const float4*>(scale + vc * 8 + 4);
-    const float4 b0 = *reinterpret_cast<const float4*>(bias + vc * 8);
-    const float4 b1 = *reinterpret_cast<const float4*>(bias + vc * 8 + 4);
-    const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-    const float bi[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-    bf16x8 o;
-    #pragma unroll
-    for (int k = 0; k < 8; ++k) o.h[k] = f2b(pw_act(acc[k] * sc[k] + bi[k], act));
-    *reinterpret_cast<uint4*>(y + i * 8) = o.v;
-  }
-}
-
-static int dwep_fail(const char* why) {
-  static __thread char msg[160];
-  snprintf(msg, sizeof(msg), "depthwise_fwd_ep: %s", why);
-  ddlw_set_error(msg);
-  return 2;
-}
-
-DDLW_EXPORT int ddlw_depthwise_fwd_ep(const void* x, const void* w_t, void* y,
-                                      const void* scale, const void* bias,
-                                      int act, int N, int H, int W_, int C,
-                                      int Ho, int Wo, int stride, int pad,
-                                      void* stream) {
-  if (C <= 0 || C % 8 != 0) return dwep_fail("C must be a positive multiple of 8");
-  if (stride != 1 && stride != 2) return dwep_fail("stride must be 1 or 2");
-  if (pad < 0) return dwep_fail("pad must be >= 0");
-  if (act < 0 || act > 2) return dwep_fail("act must be 0, 1 or 2");
-  if (!scale || !bias) return dwep_fail("scale and bias are required");
-  if (N <= 0 || H <= 0 || W_ <= 0 || Ho <= 0 || Wo <= 0)
-    return dwep_fail("empty extent");
-  if (Ho != (H + 2 * pad - 3) / stride + 1 || Wo != (W_ + 2 * pad - 3) / stride + 1)
-    return dwep_fail("output extent does not match input extent");
-  const long total = (long)N * Ho * Wo * (C >> 3);
-  long b = (total + 255) / 256;
-  const int grid = (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-  with_int<1, 2>(stride, [&](auto ST) {
-    hipLaunchKernelGGL((k_depthwise_fwd_ep<decltype(ST)::value>), dim3(grid),
-                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)w_t, (bf16_t*)y, (const float*)scale,
-                       (const float*)bias, act, N, H, W_, C, Ho, Wo, pad);
   });
   DDLW_CHECK_LAUNCH();
 }

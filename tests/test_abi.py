@@ -107,6 +107,12 @@ def test_launching_exports_end_in_stream(parsed):
                 assert re.search(r"void\s*\*\s*stream\s*$", params), name
 
 
+def test_pw_conv_fwd_has_no_dead_parameter(parsed):
+    """x, w, y, res, scale, bias, act, M, C, K, stream — no unused zero page."""
+    assert len(parsed["ddlw_pw_conv_fwd"][1]) == 11
+    assert len(abi.SIGNATURES["ddlw_pw_conv_fwd"][1]) == 11
+
+
 def test_no_call_site_bypasses_the_table():
     own = Path(abi.__file__).resolve()
     offenders = [str(f.relative_to(PKG)) for f in sorted(PKG.rglob("*.py"))
@@ -121,6 +127,35 @@ def test_symbols_resolve():
     for name, (restype, argtypes) in abi.SIGNATURES.items():
         fn = getattr(cdll, name)
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def _column_geometry(C):
+    vecC = C // 8
+    VPB = min(vecC, 256)
+    ROWG = 256 // VPB
+    return vecC, VPB, ROWG
+
+
+@pytest.mark.parametrize("C", [8, 24, 64, 2048, 2056, 4096])
+@pytest.mark.parametrize("rows", [1, 9, 255, 256, 3136, 802816])
+def test_partial_count_geometry_is_pinned(rows, C):
+    """The partial count is part of the result (it fixes the summation
+    order), so the two ``*_nparts`` queries are pinned to their formulas."""
+    if not runtime.has_lib():
+        pytest.skip("kernel library not built")
+    vecC, VPB, ROWG = _column_geometry(C)
+    need = -(-rows // ROWG)
+    assert runtime.query("bn_nparts", rows, C) == min(need, 512)
+    gx = -(-vecC // VPB)
+    assert (runtime.query("depthwise_wgrad_nparts", rows, C)
+            == max(1, min(need, max(1, 512 // gx))))
+
+
+def test_depthwise_wgrad_nparts_below_one_vector():
+    if not runtime.has_lib():
+        pytest.skip("kernel library not built")
+    for rows in (1, 256, 3136):
+        assert runtime.query("depthwise_wgrad_nparts", rows, 4) == 1
 
 
 def test_missing_symbol_names_it():

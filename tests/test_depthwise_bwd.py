@@ -24,6 +24,7 @@ SHAPES = [
     (1, 2, 2, 960, 1),    # last-stage shape at 64x64 input: every tap pads
     (1, 1, 1, 8, 1),      # single vector, single pixel
     (4, 28, 28, 32, 1),   # 3136 rows: many wgrad row-slice partials
+    (1, 3, 3, 2056, 1),   # vecC = 257: a second, partly idle wgrad block column
 ]
 ODD_S2 = (2, 15, 15, 24, 2)
 

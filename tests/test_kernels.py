@@ -22,7 +22,8 @@ def _nhwc_bf16(*shape, seed=0):
     return _cl(t)
 
 
-BN_SHAPES = [(4, 64, 56, 56), (2, 256, 28, 28), (3, 2048, 7, 7), (2, 24, 14, 14)]
+BN_SHAPES = [(4, 64, 56, 56), (2, 256, 28, 28), (3, 2048, 7, 7), (2, 24, 14, 14),
+             (2, 2056, 3, 3)]  # vecC = 257: a second, partly idle block column
 
 
 @pytest.mark.parametrize("shape", BN_SHAPES)

@@ -1,5 +1,6 @@
 """Frozen MobileNetV2 on fused kernels: the pointwise MFMA conv and the
-depthwise forward with the folded-BN epilogue (``ops/hip/pointwise.hip``),
+depthwise forward with the folded-BN epilogue (``ops/hip/pointwise.hip``,
+``k_depthwise_fwd_ep`` in ``ops/hip/depthwise.hip``),
 their block-level composition (``ops/mbconv.py``) and the model wiring.
 
 Tolerance of the kernel parity tests: inputs are exact in bf16 and both
