@@ -16,6 +16,17 @@ End to end, fused on vs ``DDLW_EVAL_FOLD=0`` (read at call time):
   - one head-training step of ``build_model(224, 224, 3, 5)``: forward, CE,
     backward, Adam.
 
+Fine-tuning (``--train``, also part of the default run): every distinct
+pointwise shape in its three training directions, our kernel against the path
+it replaces —
+  - ``fwd+stats``: ``pw_conv_fwd_stats`` + ``bn_finalize`` vs library conv +
+    ``bn_stats``;
+  - ``dgrad`` / ``wgrad``: ``pw_conv_dgrad`` / ``pw_conv_wgrad`` vs
+    ``aten.convolution_backward`` with the matching output mask;
+and one training step of ``build_model(224, 224, 3, 5, fine_tune_at=k)`` for
+k = 13 and 3, default route vs ``DDLW_PW_TRAIN=0`` (the previous behaviour).
+Same protocol, same rule (``binding.pw_train_route`` holds the verdicts).
+
 Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
 Prints one JSON line per layer shape, a table, and one final JSON line.
 """
@@ -29,6 +40,7 @@ import sys
 from pathlib import Path
 
 import torch
+import torch.nn.functional as F
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
@@ -165,6 +177,57 @@ def bench_depthwise(B, H, C, stride, dev, iters, rounds):
             "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)}
 
 
+def _conv_backward(dy, x, w, mask):
+    return torch.ops.aten.convolution_backward(
+        dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, mask)
+
+
+def bench_pointwise_train(B, H, C, K, dev, iters, rounds):
+    """fwd+stats, dgrad and wgrad of one pointwise shape: ours ("fused" in the
+    verdict's keys) against the library path it replaces ("unfused")."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    dy = _cl(torch.randn(B, K, H, H, device=dev).to(torch.bfloat16))
+    w = (torch.randn(K, C, 1, 1, device=dev) / C ** 0.5).to(torch.bfloat16)
+    w = w.contiguous(memory_format=torch.channels_last)
+    rm = torch.zeros(K, device=dev)
+    rv = torch.ones(K, device=dev)
+    M = B * H * H
+    eps, mom = 1e-5, 0.1
+
+    def fwd_ours():
+        y, ps, pq, nparts = binding.pw_conv_fwd_stats(x, w)
+        return y, binding.bn_finalize_parts(ps, pq, nparts, M, K, eps, mom, rm, rv)
+
+    def fwd_lib():
+        y = F.conv2d(x, w)
+        return y, binding.bn_stats(y, eps, mom, rm, rv)
+
+    contenders = {
+        "fwd+stats": (fwd_ours, fwd_lib, 2.0 * M * (C + K)),
+        "dgrad": (lambda: binding.pw_conv_dgrad(dy, w, x.shape),
+                  lambda: _conv_backward(dy, x, w, [True, False, False])[0],
+                  2.0 * M * (C + K)),
+        "wgrad": (lambda: binding.pw_conv_wgrad(dy, x, w.shape),
+                  lambda: _conv_backward(dy, x, w, [False, True, False])[1],
+                  2.0 * M * (C + K)),
+    }
+    recs = []
+    with torch.no_grad():
+        for direction, (ours, lib, bytes_io) in contenders.items():
+            a, b = ours(), lib()
+            a, b = (a[0], b[0]) if direction == "fwd+stats" else (a, b)
+            err = ((a.float() - b.float()).abs().max()
+                   / (b.float().abs().max() + 1e-6)).item()
+            rec = _verdict(time_interleaved({"fused": ours, "unfused": lib},
+                                            iters, rounds))
+            recs.append({"kind": "pw_" + direction, "shape": f"m{M}_c{C}_k{K}",
+                         "M": M, "C": C, "K": K, "rel_err_vs_unfused": round(err, 5),
+                         **rec,
+                         "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)})
+    return recs
+
+
 def _bf16_convs(m):
     m = m.to(memory_format=torch.channels_last)
     for mod in m.modules():
@@ -173,14 +236,52 @@ def _bf16_convs(m):
     return m
 
 
-def _with_fold(value, fn):
+def _with_env(name, value, fn):
     def run():
-        os.environ["DDLW_EVAL_FOLD"] = value
+        os.environ[name] = value
         try:
             return fn()
         finally:
-            os.environ.pop("DDLW_EVAL_FOLD", None)
+            os.environ.pop(name, None)
     return run
+
+
+def _with_fold(value, fn):
+    return _with_env("DDLW_EVAL_FOLD", value, fn)
+
+
+def bench_finetune_step(B, k, dev, iters, rounds):
+    """One training step (forward, CE, backward, Adam) of the transfer model
+    with ``features[k:]`` trainable: default route ("fused") vs
+    ``DDLW_PW_TRAIN=0`` ("unfused"), alternating in one process; a third
+    contender, ``DDLW_CONV=hip`` ("forced"), keeps the table's per-layer
+    losers on our kernels too."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
+    labels = torch.randint(0, 5, (B,), device=dev)
+    model = _bf16_convs(build_model(224, 224, 3, 5, fine_tune_at=k).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    s = time_interleaved({"fused": _with_env("DDLW_PW_TRAIN", "1", step),
+                          "unfused": _with_env("DDLW_PW_TRAIN", "0", step),
+                          "forced": _with_env("DDLW_CONV", "hip", step)},
+                         iters, rounds)
+    rec = _verdict(s)
+    rec["ms_forced"] = round(statistics.median(s["forced"]), 4)
+    rec["spread_forced"] = round(max(s["forced"]) - min(s["forced"]), 4)
+    rec["spread_fused"] = round(max(s["fused"]) - min(s["fused"]), 4)
+    for name in ("fused", "unfused"):
+        rec[f"img_s_{name}"] = round(B / rec[f"ms_{name}"] * 1e3, 1)
+    # acceptance: not slower than the contender by more than its spread
+    rec["not_slower"] = bool(rec["ms_fused"] - rec["ms_unfused"] <= rec["spread_unfused"])
+    return rec
 
 
 def bench_end_to_end(B, dev, iters, rounds):
@@ -235,6 +336,11 @@ def main():
     ap.add_argument("--e2e-iters", type=int, default=5)
     ap.add_argument("--skip-layers", action="store_true")
     ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--skip-frozen", action="store_true",
+                    help="skip the frozen-model sections")
+    ap.add_argument("--skip-train", action="store_true",
+                    help="skip the fine-tuning sections")
+    ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -242,7 +348,18 @@ def main():
     dev = torch.device("cuda:0")
     B = args.batch
     layers = []
-    if not args.skip_layers:
+    train_layers = []
+    if not args.skip_layers and not args.skip_train:
+        seen = []
+        for (H, C, K, _act, _res) in layer_shapes(224)[0]:
+            if (H, C, K) in seen:
+                continue
+            seen.append((H, C, K))
+            for rec in bench_pointwise_train(B, H, C, K, dev, args.iters, args.rounds):
+                train_layers.append(rec)
+                print(json.dumps(rec), flush=True)
+        _table(train_layers)
+    if not args.skip_layers and not args.skip_frozen:
         pw, dw = layer_shapes(224)
         for (H, C, K, act, res) in pw:
             rec = bench_pointwise(B, H, C, K, act, res, dev, args.iters, args.rounds)
@@ -253,12 +370,20 @@ def main():
             layers.append(rec)
             print(json.dumps(rec), flush=True)
         _table(layers)
-    e2e = {} if args.skip_e2e else bench_end_to_end(B, dev, args.e2e_iters, args.rounds)
+    finetune = {}
+    if not args.skip_e2e and not args.skip_train:
+        for k in args.fine_tune_at:
+            r = bench_finetune_step(B, k, dev, args.e2e_iters, args.rounds)
+            finetune[f"finetune_step_at_{k}"] = r
+            print(json.dumps({f"finetune_step_at_{k}": r}), flush=True)
+    e2e = ({} if args.skip_e2e or args.skip_frozen
+           else bench_end_to_end(B, dev, args.e2e_iters, args.rounds))
     for name, r in e2e.items():
         print(f"{name:10s} fused {r['ms_fused']:.3f} ms ({r['img_s_fused']} img/s)  "
               f"unfused {r['ms_unfused']:.3f} ms ({r['img_s_unfused']} img/s)  "
               f"spread {r['spread_unfused']:.3f}  speedup {r['speedup']}")
-    report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers, **e2e}
+    report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers,
+              "train_layers": train_layers, **finetune, **e2e}
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(report, indent=2))
@@ -266,7 +391,11 @@ def main():
                "layers_kept": sum(r["keep"] for r in layers),
                "layers_total": len(layers),
                "layers_lost": [r["shape"] for r in layers if not r["keep"]]}
-    for name, r in e2e.items():
+    summary["train_layers_kept"] = sum(r["keep"] for r in train_layers)
+    summary["train_layers_total"] = len(train_layers)
+    summary["train_layers_lost"] = [f"{r['kind']}:{r['shape']}" for r in train_layers
+                                    if not r["keep"]]
+    for name, r in {**finetune, **e2e}.items():
         summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
                                            "img_s_unfused", "speedup")}
     print(json.dumps(summary), flush=True)

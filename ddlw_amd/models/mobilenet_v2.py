@@ -39,6 +39,14 @@ from ..ops.layers import BatchNormAct2d, GlobalAvgPool2d
 from ..ops import mbconv
 
 
+def _pointwise(in_ch: int, out_ch: int) -> Conv2d:
+    """A 1x1 conv opted in to the pointwise training kernels (an instance
+    attribute: no new parameter, buffer or state_dict key)."""
+    conv = Conv2d(in_ch, out_ch, 1, bias=False)
+    conv.pw_train = True
+    return conv
+
+
 class InvertedResidual(nn.Module):
     def __init__(self, in_ch: int, out_ch: int, stride: int, expand: int):
         super().__init__()
@@ -47,7 +55,7 @@ class InvertedResidual(nn.Module):
         layers = []
         if expand != 1:
             layers += [
-                Conv2d(in_ch, hidden, 1, bias=False),
+                _pointwise(in_ch, hidden),
                 BatchNormAct2d(hidden, act="relu6"),
                 nn.Identity(),  # old ReLU6 slot (fused into the BN above)
             ]
@@ -55,7 +63,7 @@ class InvertedResidual(nn.Module):
             Conv2d(hidden, hidden, 3, stride=stride, padding=1, groups=hidden, bias=False),
             BatchNormAct2d(hidden, act="relu6"),
             nn.Identity(),
-            Conv2d(hidden, out_ch, 1, bias=False),
+            _pointwise(hidden, out_ch),
             BatchNormAct2d(out_ch),
         ]
         self.conv = nn.Sequential(*layers)
@@ -64,6 +72,10 @@ class InvertedResidual(nn.Module):
         if mbconv.inverted_residual_eval_fusable(self, x):
             # frozen block: BN folded into the conv epilogues (ops/mbconv.py)
             return mbconv.inverted_residual_eval_forward(self, x)
+        if mbconv.inverted_residual_train_fusable(self, x):
+            # trainable block: pointwise conv + BN stages with the statistics
+            # out of the conv epilogue (ops/mbconv.py)
+            return mbconv.inverted_residual_train_forward(self, x)
         return x + self.conv(x) if self.use_res else self.conv(x)
 
 
@@ -95,7 +107,7 @@ class MobileNetV2(nn.Module):
                 blocks.append(InvertedResidual(in_ch, c, s if i == 0 else 1, t))
                 in_ch = c
         blocks += [
-            Conv2d(in_ch, 1280, 1, bias=False),
+            _pointwise(in_ch, 1280),
             BatchNormAct2d(1280, act="relu6"),
             nn.Identity(),
         ]

@@ -73,6 +73,8 @@ SIGNATURES = {
     "ddlw_depthwise_wgrad": (_I, [_P, _P, _P, _P] + [_I] * 10 + [_P]),
     # pointwise.hip
     "ddlw_pw_conv_fwd": (_I, [_P] * 6 + [_I, _L, _I, _I, _P]),
+    "ddlw_pw_conv_nparts": (_I, [_L, _I, _P]),
+    "ddlw_pw_conv_fwd_stats": (_I, [_P] * 5 + [_L, _I, _I, _P]),
     # conv_gemm.hip
     "ddlw_conv_fwd_nparts": (_L, [_I] * 8),
     "ddlw_conv_fwd_igemm": (_I, [_P] * 13 + [_I] * 15 + [_P]),

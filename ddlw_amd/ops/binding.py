@@ -7,6 +7,7 @@ the kernels are stream-ordered with PyTorch ops and hipGraph-capturable.
 from __future__ import annotations
 
 import functools
+import os
 from typing import Optional
 
 import torch
@@ -303,6 +304,147 @@ def pw_conv_fwd(x: torch.Tensor, weight: torch.Tensor,
     launch("pw_conv_fwd", _nhwc(x), w2, y, res, scale, bias, int(act), rows, C,
            K)
     return y
+
+
+# ---- pointwise conv, training path ---------------------------------------- #
+
+
+def pw_train_route(direction: str, C: int, K: int, M: int) -> bool:
+    """True: this direction (``"fwd"`` = forward + BN statistics, ``"dgrad"``,
+    ``"wgrad"``) of an opted-in 1x1 conv C -> K over M rows runs on our
+    kernel; False: on the library path it replaces. The one place where a
+    measured loser is excluded (rule, table and verdicts:
+    docs/KERNELS.md, "Pointwise conv, training path")."""
+    if direction not in ("fwd", "dgrad", "wgrad"):
+        raise ValueError(f"pw_train_route: unknown direction {direction!r}")
+    if not pw_conv_supported(C, K):
+        return False
+    if os.environ.get("DDLW_CONV", "auto") == "hip":
+        return True  # force the hand-written kernels, as for every other conv
+    # The rows of the measured table (MobileNetV2 @224, batch 64) that did
+    # not beat the library by more than its spread. A verdict holds from its
+    # measured row count up; below it nothing is measured and the shape
+    # stays on our kernel.
+    if direction == "wgrad":
+        # k_conv_wgrad's 64-wide tiles are mostly empty at 16 / 24 channels
+        # and there are rows enough to show it: 0.89x, 0.97x, 0.92x
+        if (C, K) == (32, 16) and M >= 802816:
+            return False
+        if (C, K) in ((24, 144), (144, 24)) and M >= 200704:
+            return False
+        return True
+    # fwd and dgrad are the same GEMM; its loop is not software-pipelined,
+    # so a 960- or 1280-deep reduction is 30 / 40 dependent load -> MFMA
+    # steps, and at 3136 rows its 25-50 blocks leave most of the chip idle:
+    # fwd 960->160 1.11x inside the spread, 960->320 1.00x; dgrad of
+    # 160->960 0.72x, of 320->1280 0.56x. Up to one 128-row block per CU.
+    depth = C if direction == "fwd" else K
+    if depth >= 960 and 3136 <= M < 256 * 128:
+        return False
+    # 96->24 at 56x56: 1.16x, inside the library's spread
+    if direction == "fwd" and (C, K) == (96, 24) and M >= 200704:
+        return False
+    return True
+
+
+@functools.lru_cache(maxsize=512)
+def _pw_conv_nparts(rows: int, K: int) -> int:
+    return int(query("pw_conv_nparts", rows, K, None))
+
+
+def _pw_w2(weight: torch.Tensor) -> torch.Tensor:
+    """weight [K,C,1,1] (or [K,C]) -> contiguous bf16 [K][C]."""
+    w2 = weight.detach().reshape(weight.shape[0], weight.shape[1])
+    if w2.dtype != torch.bfloat16:
+        w2 = w2.to(torch.bfloat16)
+    return w2.contiguous()
+
+
+def _pw_out(x: torch.Tensor, rows: int, K: int, out, who: str) -> torch.Tensor:
+    """The [rows, K] output of a pointwise GEMM over ``x``: 4-D channels_last
+    when x is, ``out`` itself when given."""
+    shape = (x.shape[0], K, x.shape[2], x.shape[3]) if x.dim() == 4 else (rows, K)
+    if out is not None:
+        assert tuple(out.shape) == shape, f"{who}: out has the wrong shape"
+        return _nhwc(out)
+    if x.dim() == 4:
+        return torch.empty(shape, dtype=torch.bfloat16, device=x.device,
+                           memory_format=torch.channels_last)
+    return torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+
+
+def _pw_gemm(x: torch.Tensor, w2: torch.Tensor, res, out, who: str) -> torch.Tensor:
+    """``x [rows, C] * w2[K, C]^T (+ res)`` on the pointwise kernel with no
+    affine and no activation."""
+    K, C = w2.shape
+    rows, cx = _rows_c(x)
+    assert cx == C, f"{who}: input has {cx} channels, weights take {C}"
+    if not pw_conv_supported(C, K):
+        raise ValueError(f"{who}: C={C}, K={K} must be multiples of 8")
+    y = _pw_out(x, rows, K, out, who)
+    if res is not None:
+        assert res.shape == y.shape, f"{who}: acc must match the output"
+        res = _nhwc(res)
+    launch("pw_conv_fwd", _nhwc(x), w2, y, res, None, None, 0, rows, C, K)
+    return y
+
+
+def pw_conv_train_fwd(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """Training forward of a 1x1 stride-1 conv without statistics (a conv
+    whose BatchNorm is not fused to it): ``conv(x)``, bf16."""
+    return _pw_gemm(x, _pw_w2(weight), None, None, "pw_conv_train_fwd")
+
+
+def pw_conv_fwd_stats(x: torch.Tensor, weight: torch.Tensor, parts=None):
+    """Training forward of a 1x1 stride-1 conv with the BatchNorm statistics
+    of its output from the epilogue: returns ``(y, part_sum, part_sumsq,
+    nparts)`` with the partials fp32 ``[nparts, K]``, sums over the bf16
+    ``y``, for ``bn_finalize_parts``. ``parts``: a pair of contiguous fp32
+    ``[nparts, K]`` tensors to write into."""
+    w2 = _pw_w2(weight)
+    K, C = w2.shape
+    rows, cx = _rows_c(x)
+    assert cx == C, f"pw_conv_fwd_stats: x has {cx} channels, weight {C}"
+    if not pw_conv_supported(C, K):
+        raise ValueError(f"pw_conv_fwd_stats: C={C}, K={K} must be multiples of 8")
+    nparts = _pw_conv_nparts(rows, K)
+    if parts is None:
+        both = torch.empty(2, nparts, K, dtype=torch.float32, device=x.device)
+        ps, pq = both[0], both[1]
+    else:
+        ps, pq = parts
+        for t in (ps, pq):
+            assert (t.dtype == torch.float32 and t.is_contiguous()
+                    and tuple(t.shape) == (nparts, K)), "pw_conv_fwd_stats: parts"
+    y = _pw_out(x, rows, K, None, "pw_conv_fwd_stats")
+    launch("pw_conv_fwd_stats", _nhwc(x), w2, y, ps, pq, rows, C, K)
+    return y, ps, pq, nparts
+
+
+def pw_conv_dgrad(dy: torch.Tensor, weight: torch.Tensor, in_shape,
+                  acc: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None,
+                  w_t: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of a 1x1 stride-1 conv, ``dx[m][c] = sum_k dy[m][k] *
+    w[k][c] (+ acc)``: the pointwise GEMM with dy as the rows and w^T as the
+    weights. dy channels_last bf16 [N,K,H,W] (or rows [M,K]); weight
+    [K,C,1,1]; returns dx of ``in_shape``. ``acc``: dx-shaped bf16 tensor
+    added in the epilogue. ``w_t``: the bf16 [C][K] transpose if the caller
+    already holds it (else rebuilt here: weights change every step)."""
+    if w_t is None:
+        w_t = _pw_w2(weight).t().contiguous()
+    assert w_t.dtype == torch.bfloat16 and w_t.is_contiguous()
+    dx = _pw_gemm(dy, w_t, acc, out, "pw_conv_dgrad")
+    assert tuple(dx.shape) == tuple(in_shape), "pw_conv_dgrad: in_shape"
+    return dx
+
+
+def pw_conv_wgrad(dy: torch.Tensor, x: torch.Tensor, weight_shape) -> torch.Tensor:
+    """Weight gradient of a 1x1 stride-1 conv, bf16 [K,C,1,1]: the split-K
+    implicit-GEMM wgrad kernel at R = S = 1."""
+    from . import conv_gemm
+
+    return conv_gemm.conv_wgrad_kernel(dy, x, weight_shape, 1, 0)
 
 
 def depthwise_dgrad(dy: torch.Tensor, weight: torch.Tensor, in_shape,

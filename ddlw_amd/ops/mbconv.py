@@ -5,12 +5,17 @@ In a frozen base every BN is a constant per-channel affine, so it rides the
 epilogue of the conv before it: an expanded block is three kernels
 (pointwise MFMA expand + ReLU6, depthwise + ReLU6, pointwise project +
 residual) instead of conv / bn_apply pairs and an eager add.
+
+A training-mode block (the fine-tuned suffix) runs its two pointwise stages on
+``_PwConvBnActFn``: the conv kernel emits the BN statistics from its epilogue
+and the backward runs on the pointwise dgrad and the split-K wgrad kernels.
 """
 from __future__ import annotations
 
 import os
 
 import torch
+import torch.nn.functional as F
 
 from . import binding
 
@@ -90,3 +95,94 @@ def inverted_residual_eval_forward(block, x: torch.Tensor) -> torch.Tensor:
         h = conv_bn_eval(conv, bn, h)
     conv, bn = stages[-1]
     return conv_bn_eval(conv, bn, h, res=x if block.use_res else None)
+
+
+# --------------------------------------------------------------------------- #
+# Training-mode block: pointwise conv + BatchNorm stages on one Function
+# --------------------------------------------------------------------------- #
+
+
+class _PwConvBnActFn(torch.autograd.Function):
+    """conv1x1 -> BatchNormAct2d of a training-mode block. Forward: the
+    pointwise kernel writes the conv output and its BN statistics partials
+    in one pass (no ``k_bn_stats`` re-read), ``bn_finalize`` turns them into
+    mean / rstd and updates the running buffers, ``bn_apply`` normalizes.
+    Backward: BN reduce, BN dx, then the conv's dgrad and wgrad."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running_mean, running_var,
+                momentum: float, eps: float, act: int):
+        x = x.contiguous(memory_format=torch.channels_last)
+        k, c = weight.shape[0], weight.shape[1]
+        rows = x.shape[0] * x.shape[2] * x.shape[3]
+        if binding.pw_train_route("fwd", c, k, rows):
+            y, ps, pq, nparts = binding.pw_conv_fwd_stats(x, weight)
+            mean, rstd = binding.bn_finalize_parts(
+                ps, pq, nparts, rows, k, eps, momentum, running_mean,
+                running_var)
+        else:
+            y = F.conv2d(x, weight.to(x.dtype))
+            y = y.contiguous(memory_format=torch.channels_last)
+            mean, rstd = binding.bn_stats(y, eps, momentum, running_mean,
+                                          running_var)
+        out, mask = binding.bn_apply(y, None, mean, rstd, gamma, beta, act)
+        if mask is None:
+            mask = x.new_empty(0, dtype=torch.uint8)
+        ctx.save_for_backward(x, weight, y, mask, mean, rstd, gamma)
+        ctx.relu = bool(act)  # the mask bit means "gradient passes"
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .conv import pw_conv_backward
+
+        x, weight, y, mask, mean, rstd, gamma = ctx.saved_tensors
+        dout = dout.contiguous(memory_format=torch.channels_last)
+        if dout.dtype != torch.bfloat16:
+            dout = dout.to(torch.bfloat16)
+        dbeta, dgamma = binding.bn_bwd_reduce(dout, mask, y, mean, rstd, ctx.relu)
+        dy, _ = binding.bn_bwd_dx(dout, mask, y, mean, rstd, gamma, dbeta,
+                                  dgamma, ctx.relu, False)
+        dx, dw = pw_conv_backward(dy, x, weight, ctx.needs_input_grad[0],
+                                  ctx.needs_input_grad[1])
+        return dx, dw, dgamma, dbeta, None, None, None, None, None
+
+
+def pw_conv_bn_train(conv, bn, x: torch.Tensor) -> torch.Tensor:
+    """One training-mode conv1x1 + BatchNormAct2d stage on the stage
+    Function; the BN module's bookkeeping is done here as its forward does."""
+    bn.num_batches_tracked += 1
+    w, b = bn.weight, bn.bias
+    if w.dtype != torch.float32:
+        w, b = w.float(), b.float()
+    return _PwConvBnActFn.apply(x, conv.weight, w, b, bn.running_mean,
+                                bn.running_var, bn.momentum, bn.eps,
+                                _ACT[bn.act])
+
+
+def inverted_residual_train_fusable(block, x: torch.Tensor) -> bool:
+    """The conditions under which a training-mode block takes the stage
+    Function for its pointwise stages: mirrors
+    ``inverted_residual_eval_fusable`` (CUDA bf16 input, fp32 BN buffers,
+    the switches of ``conv.pw_train_enabled``, all read at call time)."""
+    from .conv import pw_train_enabled
+
+    if not block.training:
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16):
+        return False
+    if not pw_train_enabled():
+        return False
+    return all(_bn_fp32(bn) for _, bn in _stages(block))
+
+
+def inverted_residual_train_forward(block, x: torch.Tensor) -> torch.Tensor:
+    """Expand and project stages on the stage Function, the depthwise conv
+    and its BN on their modules, the residual add eager."""
+    h = x
+    for conv, bn in _stages(block):
+        if conv.pw_trainable() and bn.training:
+            h = pw_conv_bn_train(conv, bn, h)
+        else:
+            h = bn(conv(h))
+    return x + h if block.use_res else h
