@@ -77,7 +77,7 @@ SIGNATURES = {
     "ddlw_pw_conv_fwd_stats": (_I, [_P] * 5 + [_L, _I, _I, _P]),
     # conv_gemm.hip
     "ddlw_conv_fwd_nparts": (_L, [_I] * 8),
-    "ddlw_conv_fwd_igemm": (_I, [_P] * 13 + [_I] * 15 + [_P]),
+    "ddlw_conv_fwd_igemm": (_I, [_P] * 14 + [_I] * 15 + [_P]),
     "ddlw_conv_dgrad_s2m": (_I, [_P] * 4 + [_I] * 9
                             + [POINTER(c_long), POINTER(c_long), POINTER(c_int), _P]),
     # conv_wgrad.hip

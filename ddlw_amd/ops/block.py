@@ -13,6 +13,15 @@ the whole block's backward lets the join-add ride conv1's dgrad epilogue
 in a kernel that was writing that tensor anyway. Measured +1% whole-model
 step throughput on 1x MI355X.
 
+Two more passes over the block-wide tensors are gone with it. The shortcut
+gradient ``dres`` is only ``mask3 ? dy : 0``: conv1's dgrad (identity
+blocks) and bn_d's backward (downsample blocks) read ``dy`` through mask3,
+and bn3's dx kernel stops writing ``dres`` (``DDLW_FUSED_JOIN``, bit-exact).
+And the ``dy`` a block receives was written a moment ago by the next
+block's conv1 dgrad, whose epilogue emits this block's bn3 (dbeta, dgamma)
+partials on the way (``_Bn3Link``, ``DDLW_FUSED_BN3``); the Functions stay
+per block, so per-parameter gradient hooks fire as before.
+
 Numerics match the per-layer path: identical kernels in the identical
 order; the only difference is where the (bf16 + bf16) join-add rounds, and
 the fused path rounds from the fp32 accumulator (>= the engine-add's
@@ -56,6 +65,71 @@ def _wgrad_stream(device) -> "torch.cuda.Stream":
     if s is None:
         s = _wgrad_streams[device] = torch.cuda.Stream(device=device)
     return s
+
+
+def fused_join_enabled() -> bool:
+    """Residual join without a ``dres`` tensor: conv1's dgrad epilogue adds
+    ``mask3 ? dy : 0`` itself (``acc=dy, acc_mask=mask3``) and a downsample
+    BN's backward reads ``dy`` through mask3. Bit-exact against the ``dres``
+    path; DDLW_FUSED_JOIN=0 restores that path (A/B lever)."""
+    return os.environ.get("DDLW_FUSED_JOIN", "1") != "0"
+
+
+def fused_bn3_enabled() -> bool:
+    """bn3's (dbeta, dgamma) partials from the NEXT block's conv1 dgrad
+    epilogue (see ``_Bn3Link``). DDLW_FUSED_BN3=0 disables (A/B lever)."""
+    return os.environ.get("DDLW_FUSED_BN3", "1") != "0"
+
+
+class _Bn3Link:
+    """Hand-over between two consecutive fused blocks.
+
+    Block i's output gradient is written by block i+1's conv1 dgrad, whose
+    epilogue can emit the masked (dbeta, dgamma) partials of block i's bn3
+    while the values are in registers — block i's standalone
+    ``bn_bwd_reduce`` (a full re-read of dy and t3) then disappears.
+
+    Forward of block i fills ``t3/mask3/m3/s3`` and hangs the link on its
+    output tensor (``out._ddlw_bn3_link``); block i+1 picks it up from its
+    input, so any op in between yields a tensor without it and the fusion is
+    off there. Backward of block i+1 stores ``parts/nparts/dx`` and drops
+    the forward references; backward of block i uses the partials only if
+    the gradient it receives IS that ``dx`` (``matches``), and clears the
+    link either way. The link is referenced by the two Functions' ctx and by
+    that one tensor, never by a module, so it dies with the graph."""
+
+    FIELDS = ("t3", "mask3", "m3", "s3", "parts", "nparts", "dx",
+              "dx_version")
+    __slots__ = FIELDS + ("__weakref__",)
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.t3 = self.mask3 = self.m3 = self.s3 = None
+        self.parts = self.nparts = self.dx = self.dx_version = None
+
+    def armed(self) -> bool:
+        return self.t3 is not None
+
+    def take_bnb(self):
+        """The bnb tuple for block i+1's dgrad; forward references dropped
+        (one use: a second backward finds the link unarmed)."""
+        bnb = (self.t3, self.mask3, self.m3, self.s3)
+        self.t3 = self.mask3 = self.m3 = self.s3 = None
+        return bnb
+
+    def put(self, parts, nparts, dx):
+        # holding dx also keeps the engine from accumulating into it in place
+        self.parts, self.nparts, self.dx = parts, nparts, dx
+        self.dx_version = dx._version
+
+    def matches(self, dy: torch.Tensor) -> bool:
+        dx = self.dx
+        return (dx is not None and dy.data_ptr() == dx.data_ptr()
+                and dy.shape == dx.shape and dy.dtype == dx.dtype
+                and dy.stride() == dx.stride()
+                and dy._version == self.dx_version)
 
 
 def _cl(t: torch.Tensor) -> torch.Tensor:
@@ -114,7 +188,8 @@ class _BottleneckFn(torch.autograd.Function):
     conv/BN parameters (None for identity-shortcut blocks)."""
 
     @staticmethod
-    def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd, block):
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd, block,
+                link_in=None, link_out=None):
         bn1, bn2, bn3 = block.bn1, block.bn2, block.bn3
         stride = block.stride
         mode = os.environ.get("DDLW_CONV", "auto")
@@ -156,6 +231,13 @@ class _BottleneckFn(torch.autograd.Function):
                               m1, s1, m2, s2, m3, s3, md, sd)
         ctx.routes = ((r1d, r1g), (r2d, r2g), (r3d, r3g), (rdd, rdg))
         ctx.stride = stride
+        # bn3 hand-over: link_in belongs to the block that produced x,
+        # link_out to this block (the caller hangs it on the output)
+        ctx.link_in = link_in
+        ctx.link_out = link_out
+        if link_out is not None:
+            link_out.t3, link_out.mask3 = t3, mask3
+            link_out.m3, link_out.s3 = m3, s3
         return out
 
     @staticmethod
@@ -166,6 +248,14 @@ class _BottleneckFn(torch.autograd.Function):
          m1, s1, m2, s2, m3, s3, md, sd) = ctx.saved_tensors
         (r1d, r1g), (r2d, r2g), (r3d, r3g), (rdd, rdg) = ctx.routes
         stride = ctx.stride
+        link_in, link_out = ctx.link_in, ctx.link_out
+        # bn3 partials from the next block's conv1 dgrad: only if this dy is
+        # the very tensor that kernel wrote; consumed once either way
+        parts3 = None
+        if link_out is not None:
+            if link_out.matches(dy) and fused_bn3_enabled():
+                parts3 = (link_out.parts, link_out.nparts)
+            link_out.clear()
         dy = _cl(dy)
         if dy.dtype != torch.bfloat16:
             dy = dy.to(torch.bfloat16)
@@ -198,10 +288,23 @@ class _BottleneckFn(torch.autograd.Function):
             side_evs.append((done, dw))
             return dw
 
-        # bn3 (+residual, +relu): dres is the shortcut-path gradient
-        db3, dg3 = binding.bn_bwd_reduce(dy, mask3, t3, m3, s3, True)
+        # the shortcut-path gradient is mask3 ? dy : 0. Fused join: nobody
+        # materialises it — conv1's dgrad (identity) or bn_d's backward
+        # (downsample) read dy through mask3. Otherwise bn3's dx kernel
+        # writes it out as dres.
+        if not fused_join_enabled():
+            join_fused = False
+        elif wd is not None:
+            join_fused = True
+        else:
+            join_fused = bool(r1d)  # the library dgrad has no masked acc
+        if parts3 is not None:
+            db3, dg3 = binding.bn_grad_finalize_parts(
+                parts3[0][0], parts3[0][1], parts3[1], t3.shape[1])
+        else:
+            db3, dg3 = binding.bn_bwd_reduce(dy, mask3, t3, m3, s3, True)
         dt3, dres = binding.bn_bwd_dx(dy, mask3, t3, m3, s3, g3, db3, dg3,
-                                      True, True)
+                                      True, not join_fused)
         dw3 = wgrad(dt3, a2, w3, 1, 0, r3g)
         da2, db2, dg2 = _dgrad_bn_reduce(dt3, a2, w3, 1, 0, r3d,
                                          t2, mask2, m2, s2)
@@ -216,19 +319,36 @@ class _BottleneckFn(torch.autograd.Function):
         dwd = dgd = dbd = None
         if wd is not None:
             # downsample shortcut: dres -> bn_d bwd -> conv_d dgrad -> join
-            dbd, dgd = binding.bn_bwd_reduce(dres, None, td, md, sd, False)
-            dtd, _ = binding.bn_bwd_dx(dres, None, td, md, sd, gd, dbd, dgd,
-                                       False, False)
+            if join_fused:
+                dbd, dgd = binding.bn_bwd_reduce(dy, mask3, td, md, sd, True)
+                dtd, _ = binding.bn_bwd_dx(dy, mask3, td, md, sd, gd, dbd,
+                                           dgd, True, False)
+            else:
+                dbd, dgd = binding.bn_bwd_reduce(dres, None, td, md, sd, False)
+                dtd, _ = binding.bn_bwd_dx(dres, None, td, md, sd, gd, dbd,
+                                           dgd, False, False)
             dwd = wgrad(dtd, x, wd, stride, 0, rdg)
             dxd, _ = conv_gemm.conv_backward(dtd, x, wd, stride, 0, rdd, False,
                                              need_dw=False)
-            join = dxd
+            join, join_mask = dxd, None
+        elif join_fused:
+            join, join_mask = dy, mask3
         else:
-            join = dres
+            join, join_mask = dres, None
         dw1 = wgrad(dt1, x, w1, 1, 0, r1g)
-        # the join-add rides conv1's dgrad epilogue (acc=join)
-        dx, _ = conv_gemm.conv_backward(dt1, x, w1, 1, 0, r1d, False,
-                                        need_dw=False, acc=join)
+        # the join-add rides conv1's dgrad epilogue (acc=join); with a link
+        # from the previous block the same epilogue emits that block's bn3
+        # (dbeta, dgamma) partials
+        if (link_in is not None and link_in.armed() and r1d
+                and fused_bn3_enabled()):
+            dx, parts, np_ = conv_gemm.conv_dgrad_kernel(
+                dt1, w1.to(torch.bfloat16), x.shape, 0, 1, acc=join,
+                acc_mask=join_mask, bnb=link_in.take_bnb())
+            link_in.put(parts, np_, dx)
+        else:
+            dx, _ = conv_gemm.conv_backward(dt1, x, w1, 1, 0, r1d, False,
+                                            need_dw=False, acc=join,
+                                            acc_mask=join_mask)
 
         # rejoin: the optimizer (main stream) reads the dw tensors
         for done, dw in side_evs:
@@ -236,7 +356,7 @@ class _BottleneckFn(torch.autograd.Function):
             dw.record_stream(main)
 
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3,
-                dwd, dgd, dbd, None)
+                dwd, dgd, dbd, None, None, None)
 
 
 @torch.no_grad()
@@ -316,11 +436,15 @@ def bottleneck_forward(block, x: torch.Tensor) -> torch.Tensor:
         bd = block.downsample.bn.bias
     else:
         wd = gd = bd = None
-    return _BottleneckFn.apply(
+    link_in = getattr(x, "_ddlw_bn3_link", None)
+    link_out = _Bn3Link()
+    out = _BottleneckFn.apply(
         x,
         block.conv1.weight, block.bn1.weight, block.bn1.bias,
         block.conv2.weight, block.bn2.weight, block.bn2.bias,
         block.conv3.weight, block.bn3.weight, block.bn3.bias,
         wd, gd, bd,
-        block,
+        block, link_in, link_out,
     )
+    out._ddlw_bn3_link = link_out
+    return out

@@ -91,6 +91,7 @@ template <int MF, int NF, int BM, int BN, int WM, int WN, typename ACC,
           typename OutRow>
 __device__ __forceinline__ void bnb_partials_16(
     const ACC& acc, const bf16_t* __restrict__ accp,
+    const unsigned char* __restrict__ accmask,
     const bf16_t* __restrict__ bx, const unsigned char* __restrict__ bmask,
     const float* __restrict__ bmean, const float* __restrict__ brstd,
     float* __restrict__ p_db, float* __restrict__ p_dg,
@@ -122,6 +123,7 @@ __device__ __forceinline__ void bnb_partials_16(
           if (accp) {
             union { unsigned i; float f; } ca;
             ca.i = (unsigned)accp[oi] << 16;
+            if (accmask && !((accmask[oi >> 3] >> (j & 7)) & 1)) ca.f = 0.f;
             v += ca.f;
           }
           union { unsigned i; float f; } cv;
@@ -172,7 +174,13 @@ struct S2Quad {
   S2Class c[4];
 };
 
-template <int BM, int BN, bool EPI_LDS, int BUFS, bool M32EN = true>
+// ACC_EARLY (bounce epilogue only): add acc to the fp32 accumulators before
+// the bounce instead of to the bf16 values after it — see the epilogue.
+// MASKED: acc_mask is honoured. A template flag so that the unmasked
+// instantiations keep exactly the code (and the fp32 summation order of the
+// BN partials) they had.
+template <int BM, int BN, bool EPI_LDS, int BUFS, bool M32EN = true,
+          bool ACC_EARLY = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
     bf16_t* __restrict__ y, const bf16_t* __restrict__ zpage,
@@ -182,6 +190,8 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
     unsigned long long magic_wo, unsigned shift_wo,
     unsigned long long magic_ho, unsigned shift_ho,
     const bf16_t* __restrict__ accp,   // optional epilogue accumulate input
+    const unsigned char* __restrict__ acc_mask,  // optional: accp counts only
+                                       // where its bit is set (1 B / 8 ch)
     float* __restrict__ bn_ps,         // optional BN partial sums [nparts][K]
     float* __restrict__ bn_pq,         // optional BN partial sumsq
     const bf16_t* __restrict__ bnb_x,  // != null: BN-BWD mode — partials
@@ -203,6 +213,9 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
   // fuse the residual-join gradient add (d_block_input = conv1_dgrad +
   // d_identity) into the dgrad epilogue — saves the engine's separate
   // 3-pass elementwise add (read A, read B, write C) per ResNet join.
+  // acc_mask != nullptr: the add-input is taken as (bit ? accp : +0) with the
+  // bn_apply relu-mask layout (byte oi>>3, bit j&7) — the join reads dy and
+  // bn3's mask instead of a materialised masked copy of dy.
   constexpr int BK = 64;
   constexpr int WM = BM / 2, WN = BN / 2;
   constexpr int MF = WM / 16, NF = WN / 16;
@@ -480,9 +493,15 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
             if (m < M) {
               long oi = out_row(m) * K + j;
               float v = acc[mi][ni][q];
-              if (ep_scale) v = v * eps_[ni] + epb_[ni];
-              if (accp) v += b2f(accp[oi]);
-              if (ep_relu) v = fmaxf(v, 0.f);
+              if constexpr (MASKED) {
+                float a = b2f(accp[oi]);
+                if (!((acc_mask[oi >> 3] >> (j & 7)) & 1)) a = 0.f;
+                v += a;
+              } else {
+                if (ep_scale) v = v * eps_[ni] + epb_[ni];
+                if (accp) v += b2f(accp[oi]);
+                if (ep_relu) v = fmaxf(v, 0.f);
+              }
               y[oi] = f2b(v);
             }
           }
@@ -491,8 +510,8 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
       if (bn_ps) {
         if (bnb_x)
           bnb_partials_16<MF, NF, BM, BN, WM, WN>(
-              acc, accp, bnb_x, bnb_mask, bnb_mean, bnb_rstd, bn_ps, bn_pq,
-              tile_m, tile_n, wr, wc, M, K, out_row);
+              acc, accp, MASKED ? acc_mask : nullptr, bnb_x, bnb_mask, bnb_mean, bnb_rstd, bn_ps,
+              bn_pq, tile_m, tile_n, wr, wc, M, K, out_row);
         else
           bn_partials_16<MF, NF, BM, BN, WM, WN>(acc, bn_ps, bn_pq, tile_m,
                                                  tile_n, wr, wc, M, K);
@@ -502,6 +521,14 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
   }
   constexpr int WNP = WN + 8;  // pad off the bank power-of-two
   bf16_t* lC = smem + wave * (WM * WNP);
+  // A long-K shape (T > 4) bounces only because bnb forces it; on its own
+  // it takes the direct epilogue, which adds acc in fp32 BEFORE the one bf16
+  // rounding. Keep that order here, so dx does not depend on whether the
+  // reduce partials ride along: add acc to the accumulators now (the same
+  // per-element reads the direct epilogue does) and skip the add below. Its
+  // own instantiation (the launcher picks it for acc + bnb at T > 4): as a
+  // runtime branch it cost the single-K-step tiles a wave of occupancy.
+  constexpr bool acc_early = ACC_EARLY && !M32;
   if constexpr (M32) {
     #pragma unroll
     for (int mi = 0; mi < MF2; ++mi)
@@ -514,6 +541,28 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
               f2b(acc2[mi][ni][reg]);
         }
   } else {
+    if constexpr (acc_early) {
+        #pragma unroll
+        for (int mi = 0; mi < MF; ++mi) {
+          #pragma unroll
+          for (int ni = 0; ni < NF; ++ni) {
+            int j = tile_n * BN + wc * WN + ni * 16 + d_col;
+            if (j >= K) continue;
+            #pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              long m = tile_m * BM + wr * WM + mi * 16 + d_row0 + q;
+              if (m < M) {
+                long oi = out_row(m) * K + j;
+                float a = b2f(accp[oi]);
+                if constexpr (MASKED) {
+                  if (!((acc_mask[oi >> 3] >> (j & 7)) & 1)) a = 0.f;
+                }
+                acc[mi][ni][q] += a;
+              }
+            }
+          }
+        }
+    }
     #pragma unroll
     for (int mi = 0; mi < MF; ++mi)
       #pragma unroll
@@ -564,7 +613,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
     if (m < M) {
       const long orow = out_row(m);
       if (j_base + 8 <= K) {
-        if (ep_scale) {
+        if (!MASKED && ep_scale) {
           uint4 a{0, 0, 0, 0};
           if (accp)
             a = *reinterpret_cast<const uint4*>(accp + orow * K + j_base);
@@ -581,12 +630,25 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
             ow[d] = (unsigned)lo | ((unsigned)hi << 16);
           }
           *reinterpret_cast<uint4*>(y + orow * K + j_base) = o;
-        } else if (accp) {
+        } else if (accp && !acc_early) {
           // accumulate: coalesced uint4 read of the add-input at the same
           // address, pairwise bf16 add in fp32 (matches the engine's
           // bf16+bf16 add numerics)
           uint4 a = *reinterpret_cast<const uint4*>(accp + orow * K + j_base);
-          auto addpair = [&](unsigned v, unsigned aw) -> unsigned {
+          if constexpr (MASKED) {
+            // one byte covers this 8-channel chunk; a cleared bit turns
+            // its bf16 half into +0.0
+            const unsigned mb = acc_mask[(orow * K + j_base) >> 3];
+            auto keep = [&](int e) -> unsigned {
+              return (((mb >> e) & 1) ? 0xffffu : 0u) |
+                     (((mb >> (e + 1)) & 1) ? 0xffff0000u : 0u);
+            };
+            a.x &= keep(0);
+            a.y &= keep(2);
+            a.z &= keep(4);
+            a.w &= keep(6);
+          }
+          auto addpair =[&](unsigned v, unsigned aw) -> unsigned {
             bf16_t lo = f2b(b2f((bf16_t)(v & 0xffff)) + b2f((bf16_t)(aw & 0xffff)));
             bf16_t hi = f2b(b2f((bf16_t)(v >> 16)) + b2f((bf16_t)(aw >> 16)));
             return (unsigned)lo | ((unsigned)hi << 16);
@@ -635,11 +697,16 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
           if (j_base + e < K) {
             unsigned wd = (e < 2) ? val.x : (e < 4) ? val.y : (e < 6) ? val.z : val.w;
             bf16_t ov = (bf16_t)(wd >> ((e & 1) * 16));
-            if (ep_scale) {
+            if (!MASKED && ep_scale) {
               float av = accp ? b2f(accp[orow * K + j_base + e]) : 0.f;
               ov = ep_apply(ov, e, av);
-            } else if (accp)
-              ov = f2b(b2f(ov) + b2f(accp[orow * K + j_base + e]));
+            } else if (accp && !acc_early) {
+              float av = b2f(accp[orow * K + j_base + e]);
+              if constexpr (MASKED) {
+                if (!((acc_mask[(orow * K + j_base) >> 3] >> e) & 1)) av = 0.f;
+              }
+              ov = f2b(b2f(ov) + av);
+            }
             y[orow * K + j_base + e] = ov;
             if (bn_ps) {
               float f = b2f(ov);
@@ -952,9 +1019,11 @@ struct TilePick {
 
 // One tile decision for launcher + nparts query (must stay in sync by
 // construction). want_stats forces the 16x16 direct epilogue (the only
-// ones carrying the bn-partials code).
+// ones carrying the bn-partials code). want_mask (masked accumulate) lives
+// in the same two epilogues: never the wide or the 32x32 route.
 static TilePick pick_tile(long M, int K, int C, int T, bool want_stats,
-                          bool want_bnb = false, bool want_ep = false) {
+                          bool want_bnb = false, bool want_ep = false,
+                          bool want_mask = false) {
   int mfma_pref, wide_pref;
   {
     const char* e = getenv("DDLW_CONV_MFMA");
@@ -963,7 +1032,7 @@ static TilePick pick_tile(long M, int K, int C, int T, bool want_stats,
     wide_pref = e2 ? (e2[0] == '0' ? 0 : 1) : -1;  // -1 = auto
   }
   TilePick p{};
-  p.m32 = (mfma_pref == 32) && !want_stats && !want_bnb;
+  p.m32 = (mfma_pref == 32) && !want_stats && !want_bnb && !want_mask;
   // measured (bench/tools/wide_check.py + whole-model A/B on MI355X): the
   // 256x256 2-buf wide kernel wins +20-28% on its isolated shapes
   // (K >= 256, T >= 9, >= 150 blocks) but the full ResNet-50 step runs
@@ -972,7 +1041,7 @@ static TilePick pick_tile(long M, int K, int C, int T, bool want_stats,
   // isolated win). Auto routing is therefore OFF — a documented negative
   // result; DDLW_CONV_WIDE=1 forces it for probes.
   const bool wide_auto = false;
-  if (!want_bnb && !want_stats && !want_ep &&
+  if (!want_bnb && !want_stats && !want_ep && !want_mask &&
       ((wide_pref == 1 && K >= 128 && T >= 4) || (wide_pref == -1 && wide_auto))) {
     p.wide = true;
     p.bm = 256;
@@ -1008,6 +1077,9 @@ DDLW_EXPORT long ddlw_conv_fwd_nparts(int N, int C, int K, int Ho, int Wo,
 
 // The one conv-forward entry point; a null pointer switches that fusion off.
 //   acc           y += acc (residual-join gradient add in conv1's dgrad)
+//   acc_mask      with acc: y += (bit ? acc : 0), one byte per 8 output
+//                 channels in k_bn_apply's relu-mask layout, so the join reads
+//                 dy and bn3's mask instead of a masked copy of dy
 //   bn_ps/bn_pq   fused BN statistics: per-(tile_m, wave-row) sum/sumsq rows
 //   bnb_*         dgrad + fused BN-backward reduce: bn_ps/bn_pq receive the
 //                 (dbeta, dgamma) partials against (bnb_x, mask, mean, rstd),
@@ -1016,6 +1088,7 @@ DDLW_EXPORT long ddlw_conv_fwd_nparts(int N, int C, int K, int Ho, int Wo,
 //   oH/oW/oS      output scatter geometry (Ho/Wo/1 for a plain conv)
 DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
                                     const void* zpage, const void* acc,
+                                    const void* acc_mask,
                                     void* bn_ps, void* bn_pq,
                                     const void* bnb_x, const void* bnb_mask,
                                     const void* bnb_mean, const void* bnb_rstd,
@@ -1029,6 +1102,9 @@ DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
     ddlw_set_error("conv_fwd_igemm: C must be a multiple of 64");
     return 2;
   }
+  if (acc_mask && (!acc || ep_scale || K % 8 != 0))
+    return ddlw_fail("conv_fwd_igemm",
+                     "acc_mask needs acc, no ep_scale and K a multiple of 8");
   long M = (long)N * Ho * Wo;
   if (M >= (1ll << 31)) {
     ddlw_set_error("conv_fwd_igemm: M >= 2^31 unsupported");
@@ -1044,7 +1120,8 @@ DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
   const bool want_bnb = bnb_x != nullptr;
   // the eval-BN fold epilogue lives only in the base kernel
   const bool want_ep = ep_scale != nullptr;
-  TilePick p = pick_tile(M, K, C, T, want_stats, want_bnb, want_ep);
+  TilePick p = pick_tile(M, K, C, T, want_stats, want_bnb, want_ep,
+                         acc_mask != nullptr);
   if (p.wide) {
     long grid = cdiv(M, 256) * cdiv(K, p.bn);
 #define WIDE_LAUNCH(BN_, NB_)                                                  \
@@ -1063,6 +1140,49 @@ DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
 #undef WIDE_LAUNCH
     DDLW_CHECK_LAUNCH();
   }
+  if (acc && want_bnb && T > 4) {
+    // acc + bnb on a shape whose own route is the direct epilogue: the
+    // bounce epilogue with the early (fp32) accumulate, so dx is the same
+    // with and without the reduce partials
+    with_int<128, 64, 32>(p.bn, [&](auto BN) {
+     with_bool(acc_mask != nullptr, [&](auto MSK) {
+      long grid = cdiv(M, 128) * cdiv(K, decltype(BN)::value);
+      hipLaunchKernelGGL(
+          (k_conv_fwd_igemm<128, decltype(BN)::value, true, 2, false, true,
+                            decltype(MSK)::value>),
+          dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x,
+          (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage, N, H, W_, C, K,
+          Ho, Wo, R, S, stride, pad, (int)grid, oH, oW, oS, mg_wo, sh_wo,
+          mg_ho, sh_ho, (const bf16_t*)acc, (const unsigned char*)acc_mask,
+          (float*)bn_ps, (float*)bn_pq, (const bf16_t*)bnb_x,
+          (const unsigned char*)bnb_mask, (const float*)bnb_mean,
+          (const float*)bnb_rstd, nullptr, nullptr, 0);
+     });
+    });
+    DDLW_CHECK_LAUNCH();
+  }
+  if (acc_mask) {
+    // masked accumulate: its own instantiations (16x16 MFMA, no ep fold)
+    with_int<128, 64, 32>(p.bn, [&](auto BN) {
+      with_bool(p.epi_lds, [&](auto EPI) {
+        with_int<1, 2>(p.bufs, [&](auto BUFS) {
+          long grid = cdiv(M, 128) * cdiv(K, decltype(BN)::value);
+          hipLaunchKernelGGL(
+              (k_conv_fwd_igemm<128, decltype(BN)::value, decltype(EPI)::value,
+                                decltype(BUFS)::value, false, false, true>),
+              dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x,
+              (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage, N, H, W_, C,
+              K, Ho, Wo, R, S, stride, pad, (int)grid, oH, oW, oS, mg_wo,
+              sh_wo, mg_ho, sh_ho, (const bf16_t*)acc,
+              (const unsigned char*)acc_mask, (float*)bn_ps, (float*)bn_pq,
+              (const bf16_t*)bnb_x, (const unsigned char*)bnb_mask,
+              (const float*)bnb_mean, (const float*)bnb_rstd, nullptr, nullptr,
+              0);
+        });
+      });
+    });
+    DDLW_CHECK_LAUNCH();
+  }
   with_int<128, 64, 32>(p.bn, [&](auto BN) {
     with_bool(p.epi_lds, [&](auto EPI) {
       with_int<1, 2>(p.bufs, [&](auto BUFS) {
@@ -1074,7 +1194,8 @@ DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
               dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x,
               (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage, N, H, W_, C,
               K, Ho, Wo, R, S, stride, pad, (int)grid, oH, oW, oS, mg_wo,
-              sh_wo, mg_ho, sh_ho, (const bf16_t*)acc, (float*)bn_ps,
+              sh_wo, mg_ho, sh_ho, (const bf16_t*)acc,
+              (const unsigned char*)acc_mask, (float*)bn_ps,
               (float*)bn_pq, (const bf16_t*)bnb_x,
               (const unsigned char*)bnb_mask, (const float*)bnb_mean,
               (const float*)bnb_rstd, (const float*)ep_scale,
@@ -1126,7 +1247,7 @@ DDLW_EXPORT int ddlw_conv_dgrad_s2m(const void* dy, const void* wcat, void* dx,
           (const bf16_t*)wcat, (bf16_t*)dx, (const bf16_t*)zpage, N, Ho, Wo,
           Kdy, Cdx, oh, ow, 2, 2, 1, 0, (int)gx, ih, iw, 2, mg_wo, sh_wo,
           mg_ho, sh_ho, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-          nullptr, nullptr, nullptr, 0, 1, q);
+          nullptr, nullptr, nullptr, nullptr, 0, 1, q);
     });
   });
   DDLW_CHECK_LAUNCH();
