@@ -16,6 +16,13 @@ End to end, fused on vs ``DDLW_EVAL_FOLD=0`` (read at call time):
   - one head-training step of ``build_model(224, 224, 3, 5)``: forward, CE,
     backward, Adam.
 
+The stem from uint8 (``stem_u8`` row): ``stem3_u8_fwd_ep`` vs
+``normalize_u8_bf16`` + the ``Conv2d`` module + the ``BatchNormAct2d`` eval
+forward; and the two end-to-end workloads again from the uint8 batch the data
+path delivers (``base_fwd_u8``, ``head_step_u8``), default route vs
+``DDLW_STEM_U8=0``. Same alternation, same rule
+(``mbconv.stem_u8_fusable`` holds the verdict).
+
 Fine-tuning (``--train``, also part of the default run): every distinct
 pointwise shape in its three training directions, our kernel against the path
 it replaces —
@@ -177,6 +184,39 @@ def bench_depthwise(B, H, C, stride, dev, iters, rounds):
             "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)}
 
 
+def bench_stem_u8(B, size, dev, iters, rounds):
+    """The stem from a uint8 batch: ``stem3_u8_fwd_ep`` ("fused") against the
+    path it replaces ("unfused"): ``normalize_u8_bf16``, the 3->32 ``Conv2d``
+    module, the ``BatchNormAct2d`` eval forward."""
+    from ddlw_amd.ops import mbconv, normalize_u8_bf16
+
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, size, size, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    conv = Conv2d(3, 32, 3, stride=2, padding=1, bias=False).to(dev)
+    conv = conv.to(torch.bfloat16).to(memory_format=torch.channels_last).eval()
+    bn = _bn(32, 2, dev)
+    scale, bias = bn.folded_scale_bias()
+    wp = mbconv._stem3_packed(conv)
+
+    def fused():
+        return binding.stem3_u8_fwd_ep(x, conv.weight, scale, bias, 2, wp=wp)
+
+    def unfused():
+        return bn(conv(normalize_u8_bf16(x)))
+
+    with torch.no_grad():
+        ref = unfused().float()
+        err = ((fused().float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
+        rec = _verdict(time_interleaved({"fused": fused, "unfused": unfused},
+                                        iters, rounds))
+    Ho = (size - 1) // 2 + 1
+    bytes_io = 3.0 * B * size * size + 2.0 * B * Ho * Ho * 32
+    return {"kind": "stem_u8", "shape": f"n{B}_h{size}_c3_k32_s2",
+            "rel_err_vs_unfused": round(err, 5), **rec,
+            "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)}
+
+
 def _conv_backward(dy, x, w, mask):
     return torch.ops.aten.convolution_backward(
         dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, mask)
@@ -319,6 +359,45 @@ def bench_end_to_end(B, dev, iters, rounds):
     return out
 
 
+def bench_end_to_end_u8(B, dev, iters, rounds):
+    """The two end-to-end workloads fed the uint8 batch the data path
+    delivers: default route (fused stem, "fused") vs ``DDLW_STEM_U8=0``
+    (normalize + conv + ``bn_apply``, "unfused"), alternating."""
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    labels = torch.randint(0, 5, (B,), device=dev)
+    base = _bf16_convs(MobileNetV2().to(dev)).eval()
+
+    def fwd():
+        with torch.no_grad():
+            return base(x)
+
+    def pair(fn):
+        rec = _verdict(time_interleaved(
+            {"fused": _with_env("DDLW_STEM_U8", "1", fn),
+             "unfused": _with_env("DDLW_STEM_U8", "0", fn)}, iters, rounds))
+        for k in ("fused", "unfused"):
+            rec[f"img_s_{k}"] = round(B / rec[f"ms_{k}"] * 1e3, 1)
+        return rec
+
+    out = {"base_fwd_u8": pair(fwd)}
+    del base
+
+    model = _bf16_convs(build_model(224, 224, 3, 5).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    out["head_step_u8"] = pair(step)
+    return out
+
+
 def _table(recs):
     print(f"{'kind':10s} {'shape':24s} {'fused ms':>9s} {'unfused ms':>10s} "
           f"{'spread':>8s} {'speedup':>8s} {'GB/s':>8s} keep")
@@ -370,6 +449,12 @@ def main():
             layers.append(rec)
             print(json.dumps(rec), flush=True)
         _table(layers)
+    stem = []
+    if not args.skip_layers and not args.skip_frozen:
+        rec = bench_stem_u8(B, 224, dev, args.iters, args.rounds)
+        stem.append(rec)
+        print(json.dumps(rec), flush=True)
+        _table(stem)
     finetune = {}
     if not args.skip_e2e and not args.skip_train:
         for k in args.fine_tune_at:
@@ -378,12 +463,14 @@ def main():
             print(json.dumps({f"finetune_step_at_{k}": r}), flush=True)
     e2e = ({} if args.skip_e2e or args.skip_frozen
            else bench_end_to_end(B, dev, args.e2e_iters, args.rounds))
+    if e2e:
+        e2e.update(bench_end_to_end_u8(B, dev, args.e2e_iters, args.rounds))
     for name, r in e2e.items():
         print(f"{name:10s} fused {r['ms_fused']:.3f} ms ({r['img_s_fused']} img/s)  "
               f"unfused {r['ms_unfused']:.3f} ms ({r['img_s_unfused']} img/s)  "
               f"spread {r['spread_unfused']:.3f}  speedup {r['speedup']}")
     report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers,
-              "train_layers": train_layers, **finetune, **e2e}
+              "train_layers": train_layers, "stem_u8": stem, **finetune, **e2e}
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(report, indent=2))
@@ -395,6 +482,9 @@ def main():
     summary["train_layers_total"] = len(train_layers)
     summary["train_layers_lost"] = [f"{r['kind']}:{r['shape']}" for r in train_layers
                                     if not r["keep"]]
+    if stem:
+        summary["stem_u8"] = {k: stem[0][k] for k in ("ms_fused", "ms_unfused",
+                                                      "spread_unfused", "speedup", "keep")}
     for name, r in {**finetune, **e2e}.items():
         summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
                                            "img_s_unfused", "speedup")}

@@ -22,6 +22,12 @@ Activations: every BN + ReLU6 pair is one fused ``BatchNormAct2d(act=
 "relu6")``; an ``nn.Identity`` keeps the old ReLU6 slot so ``state_dict``
 keys and ``features`` indices are unchanged and saved models still load.
 
+Input: a float batch, or the ``torch.uint8`` N x C x H x W batch over NHWC
+memory (``u8_nhwc.permute(0, 3, 1, 2)``) that the decode pool and the H2D ring
+deliver — ``preprocess_input`` (``x / 127.5 - 1``) then belongs to the model,
+and on the frozen bf16 route it is fused with the stem conv, its BN and ReLU6
+into one kernel (``MobileNetV2.stem_entry``, ``ops/mbconv.py``).
+
 No pretrained weights exist in this offline environment, so the base is
 randomly initialised (documented deviation; the benchmark configs use
 random-init weights anyway, BASELINE.json).
@@ -119,19 +125,41 @@ class MobileNetV2(nn.Module):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
+    def stem_entry(self, x: torch.Tensor, frozen_stem: bool = True):
+        """The one entry for a batch, used by ``forward`` and by
+        ``FrozenBase``'s split forward: returns ``(h, start)`` and the caller
+        continues at ``features[start]``. A float batch is returned as it is
+        with ``start = 0``. A ``torch.uint8`` batch (N x C x H x W, channels_last:
+        ``u8_nhwc.permute(0, 3, 1, 2)``) is what the decode pool delivers and
+        ``preprocess_input`` belongs to the model: when the stem is frozen
+        (``frozen_stem``) and ``mbconv.stem_u8_fusable`` holds, normalize +
+        stem conv + BN + ReLU6 run as one kernel and ``start = 3``; otherwise
+        the batch is normalized once and ``start = 0``."""
+        if x.dtype != torch.uint8:
+            return x, 0
+        if frozen_stem and mbconv.stem_u8_fusable(self, x):
+            return mbconv.stem_u8_forward(self, x), 3
+        with torch.no_grad():
+            return mbconv.normalize_u8_input(x, self.features[0].weight), 0
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x, start = self.stem_entry(x)
         n = len(self.features)
         tail_conv, tail_bn = self.features[n - 3], self.features[n - 2]
         if (mbconv.eval_fold_enabled(self, x)
                 and tail_bn.running_mean.dtype == torch.float32):
             # frozen forward: the blocks fuse themselves; the 320->1280 tail
             # conv + BN + ReLU6 is one pointwise kernel as well
-            for m in self.features[: n - 3]:
+            for m in self.features[start: n - 3]:
                 x = m(x)
             return mbconv.conv_bn_eval(
                 tail_conv, tail_bn,
                 x.contiguous(memory_format=torch.channels_last))
-        return self.features(x)
+        if start == 0:
+            return self.features(x)
+        for m in self.features[start:]:
+            x = m(x)
+        return x
 
 
 class FrozenBase(nn.Module):
@@ -199,10 +227,15 @@ class FrozenBase(nn.Module):
             with torch.no_grad():
                 return self.base(x)
         feats = self.base.features
+        start = 0
         with torch.no_grad():
-            for m in feats[: self._split]:
+            if x.dtype == torch.uint8:
+                # the fused stem only where the stem is frozen (split >= 3);
+                # a trainable stem gets the normalized batch and its modules
+                x, start = self.base.stem_entry(x, frozen_stem=self._split >= 3)
+            for m in feats[start: self._split]:
                 x = m(x)
-        for m in feats[self._split:]:
+        for m in feats[max(start, self._split):]:
             x = m(x)
         return x
 

@@ -306,6 +306,54 @@ def pw_conv_fwd(x: torch.Tensor, weight: torch.Tensor,
     return y
 
 
+# ---- MobileNetV2 stem from uint8 ------------------------------------------- #
+
+
+def stem3_pack_weight(weight: torch.Tensor) -> torch.Tensor:
+    """weight [K,C,3,3] -> bf16 [K][32] for ``stem3_u8_fwd_ep``: row k holds
+    ``w[k][r][s][c]`` at ``9r + 3s + c`` (a window row is 9 contiguous input
+    bytes) and zeros from 9*C = 27 up: the 27-deep reduction as one 32-deep
+    MFMA step."""
+    K, C, r, s = weight.shape
+    assert (r, s) == (3, 3), "stem3_pack_weight: 3x3 only"
+    cols = -(-r * s * C // 32) * 32
+    wp = torch.zeros(K, cols, dtype=torch.bfloat16, device=weight.device)
+    wp[:, : r * s * C] = weight.detach().permute(0, 2, 3, 1).reshape(K, r * s * C)
+    return wp
+
+
+def stem3_u8_fwd_ep(x_u8: torch.Tensor, weight: torch.Tensor,
+                    scale: Optional[torch.Tensor] = None,
+                    bias: Optional[torch.Tensor] = None, act: int = 0,
+                    wp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The MobileNetV2 stem on a uint8 image batch in one kernel:
+    ``act(conv3x3_s2_p1(x/127.5 - 1) * scale[k] + bias[k])`` with the
+    normalized input rounded to bf16 as ``normalize_u8_bf16`` does. x_u8
+    uint8 [N,3,H,W] channels_last (NHWC memory); weight [32,3,3,3]; scale/bias
+    fp32 [32], both or neither; act 0 none / 1 ReLU / 2 ReLU6. Returns bf16
+    [N,32,Ho,Wo] channels_last. ``wp``: ``stem3_pack_weight(weight)`` if the
+    caller already holds it. Other shapes are the kernel library's to refuse."""
+    assert x_u8.is_cuda and weight.device == x_u8.device, "stem3_u8_fwd_ep: need one GPU"
+    assert x_u8.dtype == torch.uint8, f"stem3_u8_fwd_ep: need uint8, got {x_u8.dtype}"
+    assert x_u8.dim() == 4 and x_u8.is_contiguous(memory_format=torch.channels_last), \
+        "stem3_u8_fwd_ep: need a channels_last [N,C,H,W] batch"
+    n, c, h, w = x_u8.shape
+    K = weight.shape[0]
+    assert weight.shape[1] == c, f"stem3_u8_fwd_ep: x has {c} channels, weight {weight.shape[1]}"
+    if wp is None:
+        wp = stem3_pack_weight(weight)
+    assert (wp.dtype == torch.bfloat16 and wp.is_contiguous()
+            and tuple(wp.shape) == (K, -(-9 * c // 32) * 32)), "stem3_u8_fwd_ep: wp"
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    y = torch.empty((n, K, ho, wo), dtype=torch.bfloat16, device=x_u8.device,
+                    memory_format=torch.channels_last)
+    if scale is not None and bias is not None:
+        scale, bias = _f32c(scale, K), _f32c(bias, K)
+    assert all(t is None or t.device == x_u8.device for t in (wp, scale, bias))
+    launch("stem3_u8_fwd_ep", x_u8, wp, y, scale, bias, int(act), n, h, w, c, K)
+    return y
+
+
 # ---- pointwise conv, training path ---------------------------------------- #
 
 

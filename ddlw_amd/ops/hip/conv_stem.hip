@@ -471,3 +471,162 @@ DDLW_EXPORT int ddlw_stem_wgrad(const void* dy, const void* x4,
                      (const float*)slab, (bf16_t*)dw4, elems, split);
   DDLW_CHECK_LAUNCH();
 }
+
+
+// ---------------------------------------------------------------------------
+// MobileNetV2 stem from uint8: preprocess_input normalize + 3x3 stride-2 pad-1
+// conv (C=3 -> K=32) + folded BN + activation in one pass,
+//   y[n][ho][wo][k] = act((sum_{r,s,c} xn[n][2ho-1+r][2wo-1+s][c] * w[k][r][s][c])
+//                         * scale[k] + bias[k]),
+//   xn = bf16(float(u8) * (1/127.5f) - 1)            (k_normalize_u8's value)
+// uint8 NHWC in, bf16 NHWC out. The layer is bound by its output write
+// (9.6 MB in, 51 MB out at batch 64 / 224), so nothing is staged through LDS
+// and there is no barrier; the work per output vector is kept small instead.
+//   - the reduction is 27 deep; zero-padded to 32 it is ONE
+//     v_mfma_f32_16x16x32_bf16 step per 16 pixels x 16 channels. Operands as
+//     in k_pw_conv: the weight tile is A, the pixels are B, and with its
+//     weight-row order k = 8*(i>>2) + 4*f + (i&3) a lane ends up with 8
+//     consecutive output channels of one pixel = one 16-byte store.
+//   - reduction index kk = 9r + 3s + c: lane group lg = lane>>4 holds
+//     kk = 8lg .. 8lg+7 of its pixel. Window row r is 9 contiguous input bytes
+//     starting 3 bytes left of the centre column's pixel, so tap kk sits at
+//     the lane-constant byte offset (r-1)*3W + (kk-9r) - 3 from the window's
+//     centre pixel (2ho, 2wo), which always lies inside the image.
+//   - every load is ONE BYTE (rows are 3W bytes, no alignment to assume, and
+//     nothing is read past the last pixel). A tap outside the image, one of
+//     the pad slots kk >= 27, or a pixel past M loads the centre byte instead
+//     and is zeroed AFTER the normalize: padding is 0 in normalized space,
+//     not byte 0 (= -1).
+//   - the weights come repacked by the host as wp[32][32] bf16, row k holding
+//     w[k][r][s][c] at 9r + 3s + c and zeros at 27..31.
+// A wave owns 32 pixels x 32 channels, a block 4 waves = 128 pixels.
+// ---------------------------------------------------------------------------
+#define ST3_MR 2                   // 16-pixel fragments per wave
+#define ST3_WAVES 4
+#define ST3_BM (ST3_WAVES * ST3_MR * 16)
+
+// what a tap needs of its pixel's window (bits of `need` / `have`)
+#define ST3_TOP 1                  // row 2ho-1 inside the image
+#define ST3_BOT 2                  // row 2ho+1
+#define ST3_LEFT 4                 // column 2wo-1
+#define ST3_RIGHT 8                // column 2wo+1
+#define ST3_PIXEL 16               // the pixel itself: m < M
+#define ST3_NEVER 32               // a pad slot of the reduction (kk >= 27)
+
+__global__ __launch_bounds__(256) void k_stem3_u8(
+    const unsigned char* __restrict__ x,   // [N][H][W][3]
+    const bf16_t* __restrict__ wp,         // [32][32]
+    bf16_t* __restrict__ y,                // [M][32]
+    const float* __restrict__ scale, const float* __restrict__ bias, int act,
+    int M, int H, int W, int Ho, int Wo,
+    unsigned long long magic_wo, unsigned shift_wo,
+    unsigned long long magic_ho, unsigned shift_ho) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int l15 = lane & 15;
+  const int lg = lane >> 4;
+  const int m0 = blockIdx.x * ST3_BM + wave * (ST3_MR * 16);
+
+  // the lane's 8 taps: byte offset from the centre pixel, and what they need
+  int off[8], need[8];
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int kk = lg * 8 + e;
+    const int r = kk / 9, j = kk - 9 * r;  // j = 3s + c: byte in the window row
+    off[e] = (r - 1) * 3 * W + j - 3;
+    need[e] = ST3_PIXEL | (r == 0 ? ST3_TOP : 0) | (r == 2 ? ST3_BOT : 0) |
+              (j < 3 ? ST3_LEFT : 0) | (j >= 6 ? ST3_RIGHT : 0) |
+              (kk >= 27 ? ST3_NEVER : 0);
+  }
+
+  union { uint4 u; s_bf16x8_v v; } fw[2], fx[ST3_MR];
+  #pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int k = (l15 >> 2) * 8 + f * 4 + (l15 & 3);
+    fw[f].u = *reinterpret_cast<const uint4*>(wp + k * 32 + lg * 8);
+  }
+
+  #pragma unroll
+  for (int mi = 0; mi < ST3_MR; ++mi) {
+    const int m = m0 + mi * 16 + l15;
+    const unsigned mu = (unsigned)(m < M ? m : M - 1);
+    const unsigned q1 = mdiv(mu, magic_wo, shift_wo);       // n*Ho + ho
+    const int wo = (int)(mu - q1 * (unsigned)Wo);
+    const unsigned n_u = mdiv(q1, magic_ho, shift_ho);
+    const int ho = (int)(q1 - n_u * (unsigned)Ho);
+    const int have = (m < M ? ST3_PIXEL : 0) | (ho > 0 ? ST3_TOP : 0) |
+                     (2 * ho + 1 < H ? ST3_BOT : 0) | (wo > 0 ? ST3_LEFT : 0) |
+                     (2 * wo + 1 < W ? ST3_RIGHT : 0);
+    // centre pixel (2ho, 2wo): 2ho <= H-1 and 2wo <= W-1, and N*H*W*3 < 2^31
+    const unsigned char* ctr =
+        x + (((int)n_u * H + 2 * ho) * W + 2 * wo) * 3;
+    bf16x8 o;
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const bool ok = (need[e] & ~have) == 0;
+      const float v = (float)ctr[ok ? off[e] : 0] * (1.f / 127.5f) - 1.f;
+      o.h[e] = f2b(ok ? v : 0.f);
+    }
+    fx[mi].u = o.v;
+  }
+
+  s_f32x4_v acc[2][ST3_MR];
+  #pragma unroll
+  for (int f = 0; f < 2; ++f)
+    #pragma unroll
+    for (int mi = 0; mi < ST3_MR; ++mi)
+      acc[f][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          fw[f].v, fx[mi].v, s_f32x4_v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+
+  // epilogue: lane (lg, l15) holds channels 8lg .. 8lg+7 of pixel m0 + mi*16 + l15
+  float sc[8], bi[8];
+  if (scale) {
+    load8f(scale + lg * 8, sc);
+    load8f(bias + lg * 8, bi);
+  } else {
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) { sc[e] = 1.f; bi[e] = 0.f; }
+  }
+  #pragma unroll
+  for (int mi = 0; mi < ST3_MR; ++mi) {
+    const int m = m0 + mi * 16 + l15;
+    if (m >= M) continue;
+    bf16x8 o;
+    #pragma unroll
+    for (int e = 0; e < 8; ++e)
+      o.h[e] = f2b(apply_act(acc[e >> 2][mi][e & 3] * sc[e] + bi[e], act));
+    *reinterpret_cast<uint4*>(y + (long)m * 32 + lg * 8) = o.v;
+  }
+}
+
+// x uint8 [N][H][W][3]; wp bf16 [32][32] (w[k][r][s][c] at 9r + 3s + c, zeros
+// at 27..31); y bf16 [N][Ho][Wo][32] with Ho = (H-1)/2 + 1, Wo likewise;
+// scale/bias fp32 [32] (both or neither); act 0 none / 1 ReLU / 2 ReLU6.
+DDLW_EXPORT int ddlw_stem3_u8_fwd_ep(const void* x, const void* wp, void* y,
+                                     const void* scale, const void* bias,
+                                     int act, int N, int H, int W, int C,
+                                     int K, void* stream) {
+  auto fail = [](const char* why) { return ddlw_fail("stem3_u8_fwd_ep", why); };
+  if (C != 3 || K != 32) return fail("takes the 3x3 stride-2 stem with C=3, K=32");
+  if (N < 0 || H < 1 || W < 1) return fail("needs N >= 0 and H, W >= 1");
+  if (act < 0 || act > 2) return fail("act must be 0, 1 or 2");
+  if ((scale == nullptr) != (bias == nullptr))
+    return fail("scale and bias come together");
+  if ((((size_t)wp | (size_t)y | (size_t)scale | (size_t)bias) & 15) != 0)
+    return fail("wp, y, scale and bias must be 16-byte aligned");
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const long M = (long)N * Ho * Wo;
+  if (M >= (1l << 31) || (long)N * H * W * 3 >= (1l << 31))
+    return fail("N*Ho*Wo and N*H*W*3 must be below 2^31");
+  if (M == 0) return 0;
+  unsigned long long mg_wo, mg_ho;
+  unsigned sh_wo, sh_ho;
+  make_magic((unsigned)Wo, &mg_wo, &sh_wo);
+  make_magic((unsigned)Ho, &mg_ho, &sh_ho);
+  hipLaunchKernelGGL(k_stem3_u8, dim3((unsigned)cdiv(M, ST3_BM)), dim3(256), 0,
+                     (hipStream_t)stream, (const unsigned char*)x,
+                     (const bf16_t*)wp, (bf16_t*)y, (const float*)scale,
+                     (const float*)bias, act, (int)M, H, W, Ho, Wo, mg_wo,
+                     sh_wo, mg_ho, sh_ho);
+  DDLW_CHECK_LAUNCH();
+}

@@ -4,7 +4,8 @@ counterpart of ``bottleneck_eval_forward`` in ``ops/block.py``.
 In a frozen base every BN is a constant per-channel affine, so it rides the
 epilogue of the conv before it: an expanded block is three kernels
 (pointwise MFMA expand + ReLU6, depthwise + ReLU6, pointwise project +
-residual) instead of conv / bn_apply pairs and an eager add.
+residual) instead of conv / bn_apply pairs and an eager add. Fed a uint8
+batch, the frozen stem (normalize, 3->32 conv, BN, ReLU6) is one kernel too.
 
 A training-mode block (the fine-tuned suffix) runs its two pointwise stages on
 ``_PwConvBnActFn``: the conv kernel emits the BN statistics from its epilogue
@@ -95,6 +96,85 @@ def inverted_residual_eval_forward(block, x: torch.Tensor) -> torch.Tensor:
         h = conv_bn_eval(conv, bn, h)
     conv, bn = stages[-1]
     return conv_bn_eval(conv, bn, h, res=x if block.use_res else None)
+
+
+# --------------------------------------------------------------------------- #
+# Stem from a uint8 image batch: normalize + conv + BN + ReLU6 in one kernel
+# --------------------------------------------------------------------------- #
+
+
+def _is_stem3(conv) -> bool:
+    return (conv.in_channels == 3 and conv.out_channels == 32
+            and conv.kernel_size == (3, 3) and conv.stride == (2, 2)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is None
+            and conv.weight.dtype == torch.bfloat16)
+
+
+def stem_u8_fusable(net, x) -> bool:
+    """The conditions under which ``net.features[0:3]`` (stem conv,
+    BatchNormAct2d, the old ReLU6 slot) of a MobileNetV2 takes a uint8 batch
+    on ``binding.stem3_u8_fwd_ep``: ``eval_fold_enabled``'s with uint8 in
+    place of bf16 (stem children in eval mode, no grad, CUDA input, the three
+    switches), fp32 BN statistics, the 3->32 3x3 stride-2 pad-1 bias-free
+    conv with bf16 weights, a channels_last batch, and the A/B switch
+    ``DDLW_STEM_U8`` (default ``1``) not ``0``. All read at call time.
+    No measured-loser predicate: the fused stem beat normalize + conv +
+    ``bn_apply`` by more than their spread at batch 64 / 224
+    (bench/bench_mobilenet.py; rows in docs/KERNELS.md)."""
+    if torch.is_grad_enabled() or any(m.training for m in net.features[:3]):
+        return False
+    if not (x.is_cuda and x.dtype == torch.uint8):
+        return False
+    if os.environ.get("DDLW_DISABLE_HIP_OPS", "0") == "1":
+        return False
+    if os.environ.get("DDLW_EVAL_FOLD", "1") != "1":
+        return False
+    if os.environ.get("DDLW_CONV", "auto") == "stock":
+        return False
+    if os.environ.get("DDLW_STEM_U8", "1") == "0":
+        return False
+    conv, bn = net.features[0], net.features[1]
+    if not (_is_stem3(conv) and _bn_fp32(bn)):
+        return False
+    return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+
+
+def _stem3_packed(conv) -> torch.Tensor:
+    """``binding.stem3_pack_weight(conv.weight)``, cached on the module until
+    the weight mutates or moves (as ``folded_scale_bias`` caches)."""
+    w = conv.weight
+    key = (w._version, w.data_ptr(), w.device)
+    cached = getattr(conv, "_stem3_cache", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    wp = binding.stem3_pack_weight(w)
+    conv._stem3_cache = (key, wp)
+    return wp
+
+
+@torch.no_grad()
+def stem_u8_forward(net, x: torch.Tensor) -> torch.Tensor:
+    """``features[0:3]`` of a frozen MobileNetV2 on a uint8 batch: one
+    launch (``stem_u8_fusable`` is the caller's to check)."""
+    conv, bn = net.features[0], net.features[1]
+    scale, bias = bn.folded_scale_bias()
+    return binding.stem3_u8_fwd_ep(x, conv.weight, scale, bias, _ACT[bn.act],
+                                   wp=_stem3_packed(conv))
+
+
+def normalize_u8_input(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """The ``preprocess_input`` normalize of a uint8 batch for a stem the
+    fused kernel does not take: ``normalize_u8_bf16`` (what callers ran
+    themselves) for bf16 stem weights on CUDA, else fp32 ``x / 127.5 - 1``
+    (``data.preprocess.normalize_uint8``) cast to the weight's dtype."""
+    if x.is_cuda and weight.dtype == torch.bfloat16:
+        from .layers import normalize_u8_bf16
+
+        if x.dim() == 4:
+            x = x.contiguous(memory_format=torch.channels_last)
+        return normalize_u8_bf16(x)
+    return (x.to(torch.float32) / 127.5 - 1.0).to(weight.dtype)
 
 
 # --------------------------------------------------------------------------- #
