@@ -20,17 +20,14 @@ def trial(params):
     import torch
 
     from ddlw_amd.models import build_resnet50
-    from ddlw_amd.ops import FusedSGD, require_lib, softmax_cross_entropy
+    from ddlw_amd.ops import FusedSGD, apply_bf16_policy, require_lib, softmax_cross_entropy
 
     steps = int(params["steps"])
     batch = int(params["batch"])
     device = torch.device("cuda:0")
     require_lib()
     torch.manual_seed(0)
-    model = build_resnet50(num_classes=1000).to(device).to(memory_format=torch.channels_last)
-    for m in model.modules():
-        if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear)):
-            m.to(torch.bfloat16)
+    model = apply_bf16_policy(build_resnet50(num_classes=1000).to(device))
     opt = FusedSGD(model.parameters(), lr=params["lr"], momentum=0.9)
     x = torch.randn(batch, 3, 224, 224, device=device).to(torch.bfloat16).contiguous(
         memory_format=torch.channels_last

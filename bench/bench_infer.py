@@ -35,12 +35,11 @@ class ResNetPyFunc(PythonModel):
         self.model = load_torch(context.artifacts["model"])
         self.model.eval()
         if torch.cuda.is_available():
-            self.model = self.model.cuda().to(memory_format=torch.channels_last)
+            from ddlw_amd.ops import apply_bf16_policy
+
             # bf16 conv/fc weights ONCE (BN stats stay fp32 — the eval-BN
             # fold reads them); avoids per-batch autocast weight casts
-            for m in self.model.modules():
-                if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear)):
-                    m.to(torch.bfloat16)
+            self.model = apply_bf16_policy(self.model.cuda())
 
     def predict(self, context, model_input):
         import functools

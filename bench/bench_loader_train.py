@@ -56,7 +56,8 @@ def main() -> None:
     from ddlw_amd.data.loader import make_converter
     from ddlw_amd.data.synthetic import make_synthetic_dataset
     from ddlw_amd.models import build_resnet50
-    from ddlw_amd.ops import FusedSGD, normalize_u8_bf16, require_lib, softmax_cross_entropy
+    from ddlw_amd.ops import (FusedSGD, apply_bf16_policy, normalize_u8_bf16, require_lib,
+                              softmax_cross_entropy)
 
     assert torch.cuda.is_available(), "config-2 bench needs a GPU"
     require_lib()
@@ -70,10 +71,7 @@ def main() -> None:
     conv = make_converter(table, row_group_rows=64)
 
     torch.manual_seed(1234)
-    model = build_resnet50(num_classes=5).to(device).to(memory_format=torch.channels_last)
-    for m in model.modules():
-        if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear)):
-            m.to(torch.bfloat16)
+    model = apply_bf16_policy(build_resnet50(num_classes=5).to(device))
     opt = FusedSGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4)
     model.train()
 

@@ -34,6 +34,14 @@ and one training step of ``build_model(224, 224, 3, 5, fine_tune_at=k)`` for
 k = 13 and 3, default route vs ``DDLW_PW_TRAIN=0`` (the previous behaviour).
 Same protocol, same rule (``binding.pw_train_route`` holds the verdicts).
 
+The facade (``facade_head_step_u8``): the head-training step from a uint8
+batch through ``train.Model(precision="bf16")``, through ``Model(precision=
+"fp32")`` on the normalized fp32 batch, and as the hand loop — three
+contenders alternating. The optimizer (``adadelta_step_*``): one
+``FusedAdadelta`` step vs ``torch.optim.Adadelta(foreach=True)`` over the fp32
+trainable parameters of ``fine_tune_at=13`` and of the head alone; recorded
+only.
+
 Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
 Prints one JSON line per layer shape, a table, and one final JSON line.
 """
@@ -52,7 +60,8 @@ import torch.nn.functional as F
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from ddlw_amd.models.mobilenet_v2 import _V2_CFG, MobileNetV2, build_model  # noqa: E402
-from ddlw_amd.ops import FusedAdam, binding, softmax_cross_entropy  # noqa: E402
+from ddlw_amd.ops import (FusedAdadelta, FusedAdam, apply_bf16_policy,  # noqa: E402
+                          binding, softmax_cross_entropy)
 from ddlw_amd.ops.conv import Conv2d  # noqa: E402
 from ddlw_amd.ops.layers import BatchNormAct2d  # noqa: E402
 
@@ -268,14 +277,6 @@ def bench_pointwise_train(B, H, C, K, dev, iters, rounds):
     return recs
 
 
-def _bf16_convs(m):
-    m = m.to(memory_format=torch.channels_last)
-    for mod in m.modules():
-        if isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear)):
-            mod.to(torch.bfloat16)
-    return m
-
-
 def _with_env(name, value, fn):
     def run():
         os.environ[name] = value
@@ -299,7 +300,7 @@ def bench_finetune_step(B, k, dev, iters, rounds):
     torch.manual_seed(0)
     x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
     labels = torch.randint(0, 5, (B,), device=dev)
-    model = _bf16_convs(build_model(224, 224, 3, 5, fine_tune_at=k).to(dev)).train()
+    model = apply_bf16_policy(build_model(224, 224, 3, 5, fine_tune_at=k).to(dev)).train()
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4)
 
     def step():
@@ -328,7 +329,7 @@ def bench_end_to_end(B, dev, iters, rounds):
     torch.manual_seed(0)
     x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
     labels = torch.randint(0, 5, (B,), device=dev)
-    base = _bf16_convs(MobileNetV2().to(dev)).eval()
+    base = apply_bf16_policy(MobileNetV2().to(dev)).eval()
 
     def fwd():
         with torch.no_grad():
@@ -341,7 +342,7 @@ def bench_end_to_end(B, dev, iters, rounds):
         out["base_fwd"][f"img_s_{k}"] = round(B / out["base_fwd"][f"ms_{k}"] * 1e3, 1)
     del base
 
-    model = _bf16_convs(build_model(224, 224, 3, 5).to(dev)).train()
+    model = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).train()
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
 
     def step():
@@ -367,7 +368,7 @@ def bench_end_to_end_u8(B, dev, iters, rounds):
     u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
     x = u8.permute(0, 3, 1, 2)
     labels = torch.randint(0, 5, (B,), device=dev)
-    base = _bf16_convs(MobileNetV2().to(dev)).eval()
+    base = apply_bf16_policy(MobileNetV2().to(dev)).eval()
 
     def fwd():
         with torch.no_grad():
@@ -384,7 +385,7 @@ def bench_end_to_end_u8(B, dev, iters, rounds):
     out = {"base_fwd_u8": pair(fwd)}
     del base
 
-    model = _bf16_convs(build_model(224, 224, 3, 5).to(dev)).train()
+    model = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).train()
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
 
     def step():
@@ -396,6 +397,80 @@ def bench_end_to_end_u8(B, dev, iters, rounds):
 
     out["head_step_u8"] = pair(step)
     return out
+
+
+def _stats(samples: dict, B=None) -> dict:
+    out = {}
+    for k, v in samples.items():
+        out[f"ms_{k}"] = round(statistics.median(v), 4)
+        out[f"spread_{k}"] = round(max(v) - min(v), 4)
+        if B is not None:
+            out[f"img_s_{k}"] = round(B / statistics.median(v) * 1e3, 1)
+    return out
+
+
+def bench_facade_step(B, dev, iters, rounds):
+    """The head-training step of ``build_model(224, 224, 3, 5)`` from a uint8
+    batch, three ways, alternating: ``train.Model(precision="bf16")``
+    ("facade_bf16"), ``Model(precision="fp32")`` on the normalized fp32 NCHW
+    batch ("facade_fp32", what the examples run by default) and the hand loop
+    of ``bench_end_to_end_u8`` ("hand"). The claim: the bf16 median beats the
+    fp32 median by more than the fp32 spread (``bf16_beats_fp32``)."""
+    from ddlw_amd.train import Model
+
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
+    x32 = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0).contiguous()
+    labels = torch.randint(0, 5, (B,), device=dev)
+
+    m16 = Model(build_model(224, 224, 3, 5), dev, precision="bf16")
+    m16.compile("Adam", learning_rate=1e-3)
+    m32 = Model(build_model(224, 224, 3, 5).to(dev), dev, precision="fp32")
+    m32.compile("Adam", learning_rate=1e-3)
+
+    hand = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).train()
+    opt = FusedAdam([p for p in hand.parameters() if p.requires_grad], lr=1e-3)
+    xh = u8.permute(0, 3, 1, 2)
+
+    def hand_step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(hand(xh), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    s = time_interleaved({"facade_bf16": lambda: m16.train_step(u8, labels),
+                          "facade_fp32": lambda: m32.train_step(x32, labels),
+                          "hand": hand_step}, iters, rounds)
+    rec = _stats(s, B)
+    rec["bf16_beats_fp32"] = bool(
+        rec["ms_facade_fp32"] - rec["ms_facade_bf16"] > rec["spread_facade_fp32"])
+    rec["facade_minus_hand_ms"] = round(rec["ms_facade_bf16"] - rec["ms_hand"], 4)
+    return rec
+
+
+def bench_adadelta_step(k, dev, iters, rounds):
+    """One optimizer step over the trainable fp32 parameters of
+    ``build_model(..., fine_tune_at=k)`` (``None``: the head alone):
+    ``FusedAdadelta`` ("fused") vs ``torch.optim.Adadelta(foreach=True)``
+    ("unfused"). Recorded only: under bf16 the fused kernel is a matter of
+    correctness, so no routing depends on it."""
+    torch.manual_seed(0)
+    model = build_model(224, 224, 3, 5, fine_tune_at=k).to(dev)
+    sets = []
+    for _ in range(2):
+        ps = [torch.nn.Parameter(p.detach().clone()) for p in model.parameters()
+              if p.requires_grad]
+        for p in ps:
+            p.grad = torch.randn_like(p) * 0.01
+        sets.append(ps)
+    fused = FusedAdadelta(sets[0], lr=1.0)
+    stock = torch.optim.Adadelta(sets[1], lr=1.0, foreach=True)
+    rec = _verdict(time_interleaved({"fused": fused.step, "unfused": stock.step},
+                                    iters, rounds))
+    rec["tensors"] = len(sets[0])
+    rec["numel"] = sum(p.numel() for p in sets[0])
+    return rec
 
 
 def _table(recs):
@@ -419,6 +494,8 @@ def main():
                     help="skip the frozen-model sections")
     ap.add_argument("--skip-train", action="store_true",
                     help="skip the fine-tuning sections")
+    ap.add_argument("--skip-facade", action="store_true",
+                    help="skip the Model-facade and Adadelta-step sections")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -465,12 +542,21 @@ def main():
            else bench_end_to_end(B, dev, args.e2e_iters, args.rounds))
     if e2e:
         e2e.update(bench_end_to_end_u8(B, dev, args.e2e_iters, args.rounds))
+    facade = {}
+    if not args.skip_facade:
+        r = bench_facade_step(B, dev, args.e2e_iters, args.rounds)
+        facade["facade_head_step_u8"] = r
+        print(json.dumps({"facade_head_step_u8": r}), flush=True)
+        for k, name in ((13, "adadelta_step_at_13"), (None, "adadelta_step_head")):
+            r = bench_adadelta_step(k, dev, args.iters, args.rounds)
+            facade[name] = r
+            print(json.dumps({name: r}), flush=True)
     for name, r in e2e.items():
         print(f"{name:10s} fused {r['ms_fused']:.3f} ms ({r['img_s_fused']} img/s)  "
               f"unfused {r['ms_unfused']:.3f} ms ({r['img_s_unfused']} img/s)  "
               f"spread {r['spread_unfused']:.3f}  speedup {r['speedup']}")
     report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers,
-              "train_layers": train_layers, "stem_u8": stem, **finetune, **e2e}
+              "train_layers": train_layers, "stem_u8": stem, **finetune, **e2e, **facade}
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(report, indent=2))
@@ -488,6 +574,7 @@ def main():
     for name, r in {**finetune, **e2e}.items():
         summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
                                            "img_s_unfused", "speedup")}
+    summary.update(facade)
     print(json.dumps(summary), flush=True)
 
 

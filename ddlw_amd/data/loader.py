@@ -47,6 +47,15 @@ def _default_transform(content, img_height: int, img_width: int):
     return preprocess_bytes(content, img_height, img_width)
 
 
+def _uint8_transform(content, img_height: int, img_width: int):
+    # ``output="uint8"``: HWC uint8, normalization left to the device.
+    # Module-level (picklable) like the default; decode.py imports this
+    # module, hence the import here.
+    from .decode import decode_resize_u8
+
+    return torch.from_numpy(np.array(decode_resize_u8(content, img_height, img_width)))
+
+
 _forkserver_preloaded = False
 
 
@@ -255,7 +264,13 @@ class _H2DStager:
 
 
 class ShardedParquetLoader:
-    """Iterates (images, labels) batches from a Parquet dataset shard."""
+    """Iterates (images, labels) batches from a Parquet dataset shard.
+
+    ``output="float"`` (default): fp32 N x C x H x W in [-1, 1].
+    ``output="uint8"``: the decoded bytes, N x H x W x C — a quarter of the
+    H2D traffic; the normalize then belongs to the model
+    (``train.Model(precision="bf16")`` takes these batches as they are).
+    A custom ``transform=`` replaces either and excludes ``output="uint8"``."""
 
     def __init__(
         self,
@@ -273,6 +288,7 @@ class ShardedParquetLoader:
         transform: Optional[Callable] = None,
         prefetch: int = 2,
         pool: str = "auto",  # "process" | "thread" | "auto"
+        output: str = "float",  # "float": fp32 CHW in [-1, 1] | "uint8": HWC bytes
     ):
         self.path = str(dataset_path)
         self.files = sorted(str(p) for p in Path(self.path).glob("*.parquet")) or [self.path]
@@ -288,9 +304,16 @@ class ShardedParquetLoader:
         self.label_column = label_column
         import functools
 
+        if output not in ("float", "uint8"):
+            raise ValueError(f"output must be float|uint8, got {output!r}")
+        if transform is not None and output == "uint8":
+            raise ValueError(
+                "transform= and output='uint8' both choose the decode step; "
+                "give one of them")
+        self.output = output
         self.transform = transform or functools.partial(
-            _default_transform, img_height=self.img_height,
-            img_width=self.img_width)
+            _uint8_transform if output == "uint8" else _default_transform,
+            img_height=self.img_height, img_width=self.img_width)
         self.prefetch = prefetch
         if pool not in ("auto", "process", "thread"):
             raise ValueError(f"pool must be auto|process|thread, got {pool!r}")

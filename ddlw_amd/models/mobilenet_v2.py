@@ -100,6 +100,8 @@ _V2_CFG = [
 class MobileNetV2(nn.Module):
     """Feature extractor (include_top=False): output B x 1280 x H/32 x W/32."""
 
+    accepts_uint8 = True  # ``stem_entry`` normalizes; read by ops.prepare_batch
+
     def __init__(self, channels: int = 3):
         super().__init__()
         blocks = [
@@ -173,6 +175,8 @@ class FrozenBase(nn.Module):
     freezes everything, with the whole base in one ``no_grad`` forward.
     """
 
+    accepts_uint8 = True  # hands a uint8 batch to ``base.stem_entry``
+
     def __init__(self, base: nn.Module, fine_tune_at: Optional[int] = None):
         super().__init__()
         self.base = base
@@ -244,6 +248,8 @@ class TransferModel(nn.Module):
     """Frozen base -> GAP -> Dropout -> Dense(num_classes) logits
     (reference ``.../02_model_training_single_node.py:171-176``).
     ``fine_tune_at``: see ``FrozenBase``."""
+
+    accepts_uint8 = True  # the base takes the uint8 batch
 
     def __init__(self, channels: int = 3, num_classes: int = 5, dropout: float = 0.5,
                  fine_tune_at: Optional[int] = None):

@@ -18,8 +18,9 @@ from .layers import (
     softmax_cross_entropy,
     normalize_u8_bf16,
 )
-from .optim import FusedSGD, FusedAdam
+from .optim import FusedSGD, FusedAdam, FusedAdadelta
 from .conv import Conv2d
+from .precision import apply_bf16_policy, prepare_batch
 
 __all__ = [
     "lib",
@@ -33,5 +34,8 @@ __all__ = [
     "normalize_u8_bf16",
     "FusedSGD",
     "FusedAdam",
+    "FusedAdadelta",
     "Conv2d",
+    "apply_bf16_policy",
+    "prepare_batch",
 ]

@@ -65,6 +65,7 @@ SIGNATURES = {
     # optim.hip
     "ddlw_fused_sgd": (_I, [_P, _I, _L, _F, _F, _F, _I, _P]),
     "ddlw_fused_adam": (_I, [_P, _I, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "ddlw_fused_adadelta": (_I, [_P, _I, _L, _F, _F, _F, _F, _P]),
     # depthwise.hip
     "ddlw_depthwise_fwd": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_depthwise_fwd_ep": (_I, [_P] * 5 + [_I] * 9 + [_P]),

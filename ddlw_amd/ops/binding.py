@@ -208,6 +208,15 @@ def fused_adam(chunk_desc: torch.Tensor, nchunks: int, max_numel: int,
            weight_decay, bc1, bc2)
 
 
+def fused_adadelta(chunk_desc: torch.Tensor, nchunks: int, max_numel: int,
+                   lr: float, rho: float, eps: float, weight_decay: float):
+    """chunk_desc: int64 device tensor [nchunks, 7] of
+    (p_ptr, g_ptr, square_avg_ptr, acc_delta_ptr, p_bf16_ptr_or_0, numel,
+    flags)."""
+    launch("fused_adadelta", chunk_desc, nchunks, max_numel, lr, rho, eps,
+           weight_decay)
+
+
 def _depthwise_w_t(weight: torch.Tensor) -> torch.Tensor:
     """weight [C,1,R,S] -> bf16 [R*S][C], so taps read contiguous channel
     vectors."""

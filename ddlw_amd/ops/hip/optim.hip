@@ -101,3 +101,55 @@ DDLW_EXPORT int ddlw_fused_adam(const void* chunks, int nchunks, long max_numel,
                      weight_decay, bc1, bc2);
   DDLW_CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------------------
+// Fused Adadelta (K10 — the other optimizer of the reference's HPO space,
+// hp.choice('optimizer', ['Adadelta', 'Adam']); P2/01:195). Same layout as
+// Adam: fp32 master, square_avg and acc_delta, optional bf16 param shadow,
+// grads fp32 or bf16. The update is a ratio of two running RMS values and is
+// often far below one bf16 ulp of the weight, so all of it stays in fp32.
+// ---------------------------------------------------------------------------
+struct AdadeltaChunk {
+  float* p;        // fp32 master
+  const void* g;   // grad (fp32, or bf16 when flags & 1)
+  float* sq;       // running average of g^2
+  float* acc;      // running average of delta^2
+  bf16_t* p_bf16;  // nullable bf16 shadow
+  long n;
+  long flags;
+};
+
+__global__ __launch_bounds__(256) void k_fused_adadelta(
+    const AdadeltaChunk* __restrict__ chunks, int nchunks, float lr, float rho,
+    float eps, float weight_decay) {
+  for (int ci = blockIdx.y; ci < nchunks; ci += gridDim.y) {
+    AdadeltaChunk ch = chunks[ci];
+    const bool g_bf16 = ch.flags & 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < ch.n;
+         i += (long)gridDim.x * blockDim.x) {
+      float g = g_bf16 ? b2f(((const bf16_t*)ch.g)[i])
+                       : ((const float*)ch.g)[i];
+      float p = ch.p[i];
+      g += weight_decay * p;
+      float sq = rho * ch.sq[i] + (1.f - rho) * g * g;
+      float acc = ch.acc[i];
+      float delta = sqrtf(acc + eps) / sqrtf(sq + eps) * g;
+      ch.sq[i] = sq;
+      ch.acc[i] = rho * acc + (1.f - rho) * delta * delta;
+      p -= lr * delta;
+      ch.p[i] = p;
+      if (ch.p_bf16) ch.p_bf16[i] = f2b(p);
+    }
+  }
+}
+
+DDLW_EXPORT int ddlw_fused_adadelta(const void* chunks, int nchunks,
+                                    long max_numel, float lr, float rho,
+                                    float eps, float weight_decay,
+                                    void* stream) {
+  dim3 grid(grid_1d(max_numel, 256, 512), min(nchunks, 64));
+  hipLaunchKernelGGL(k_fused_adadelta, grid, dim3(256), 0, (hipStream_t)stream,
+                     (const AdadeltaChunk*)chunks, nchunks, lr, rho, eps,
+                     weight_decay);
+  DDLW_CHECK_LAUNCH();
+}

@@ -9,6 +9,9 @@ Momentum + weight decay. Two parameter classes:
   all in the same pass (mixed-precision SGD exactly like the reference's
   LossScale-free bf16 recipe).
 
+``FusedAdam`` and ``FusedAdadelta`` below follow the same two-class layout
+with their own fp32 state.
+
 Momentum buffers start at zero, so v = mu*v + g reproduces torch.optim.SGD's
 buf-initialized-to-grad first step. The chunk descriptor table is built once
 per group and refreshed only if grad storage moves, so the steady-state step
@@ -246,5 +249,100 @@ class FusedAdam(torch.optim.Optimizer):
                 desc, len(params), max_numel, group["lr"], b1, b2,
                 group["eps"], group["weight_decay"],
                 1.0 / (1.0 - b1 ** t), 1.0 / (1.0 - b2 ** t),
+            )
+        return loss
+
+
+class FusedAdadelta(torch.optim.Optimizer):
+    """Fused Adadelta (kernel K10 — the second optimizer of the reference's
+    HPO space, ``hp.choice('optimizer', ['Adadelta', 'Adam'])`` at P2/01:195):
+    one multi-tensor kernel per step with the math of ``torch.optim.Adadelta``
+    in fp32; fp32 square_avg / acc_delta (+ fp32 master for bf16 params with
+    the bf16 shadow updated in the same pass). An Adadelta update is a ratio
+    of two running RMS values times the grad and is usually far below one
+    bf16 ulp of the weight, so on bf16 params the stock optimizer mostly
+    rounds it away; the master keeps it."""
+
+    def __init__(self, params, lr: float = 1.0, rho: float = 0.9,
+                 eps: float = 1e-6, weight_decay: float = 0.0):
+        defaults = dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+        self._desc: Dict[int, Tuple[tuple, torch.Tensor, int]] = {}
+
+    def _state_for(self, p: torch.Tensor):
+        st = self.state[p]
+        if "square_avg" not in st:
+            if p.dtype == torch.bfloat16:
+                st["master"] = p.detach().float()
+                base = st["master"]
+            else:
+                base = p
+            st["square_avg"] = torch.zeros_like(base)
+            st["acc_delta"] = torch.zeros_like(base)
+        return st
+
+    def _group_desc(self, gi: int, params: List[torch.Tensor]):
+        key = tuple((p.data_ptr(), p.grad.data_ptr(), p.numel()) for p in params)
+        cached = self._desc.get(gi)
+        if cached is not None and cached[0] == key:
+            return cached[1], cached[2]
+        rows = []
+        max_numel = 0
+        for p in params:
+            st = self._state_for(p)
+            if p.dtype == torch.bfloat16:
+                rows.append(
+                    (st["master"].data_ptr(), p.grad.data_ptr(),
+                     st["square_avg"].data_ptr(), st["acc_delta"].data_ptr(),
+                     p.data_ptr(), p.numel(),
+                     1 if p.grad.dtype == torch.bfloat16 else 0)
+                )
+            else:
+                assert p.grad.dtype == torch.float32, p.grad.dtype
+                rows.append(
+                    (p.data_ptr(), p.grad.data_ptr(), st["square_avg"].data_ptr(),
+                     st["acc_delta"].data_ptr(), 0, p.numel(), 0)
+                )
+            max_numel = max(max_numel, p.numel())
+        cpu = torch.tensor(rows, dtype=torch.int64).pin_memory()
+        desc = cpu.to(params[0].device, non_blocking=True)
+        # keep the pinned source alive until at least the next rebuild (the
+        # async H2D may still be reading it when this function returns)
+        self._desc[gi] = (key, desc, max_numel, cpu)
+        return desc, max_numel
+
+    def load_state_dict(self, state_dict):
+        # no-cast load (fp32 master/square_avg/acc_delta of bf16 params must
+        # stay fp32 for the raw-pointer fused kernel); invalidate the
+        # descriptor cache holding raw pointers into the replaced state
+        _load_state_dict_no_cast(self, state_dict)
+        self._desc.clear()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for gi, group in enumerate(self.param_groups):
+            params = [p for p in group["params"] if p.grad is not None]
+            if not params:
+                continue
+            rho, eps = group["rho"], group["eps"]
+            if not params[0].is_cuda:
+                for p in params:
+                    st = self._state_for(p)
+                    master = st.get("master")
+                    tgt = master if master is not None else p
+                    g = p.grad.float() + group["weight_decay"] * tgt
+                    sq, acc = st["square_avg"], st["acc_delta"]
+                    sq.mul_(rho).addcmul_(g, g, value=1 - rho)
+                    delta = acc.add(eps).sqrt_().div_(sq.add(eps).sqrt_()).mul_(g)
+                    acc.mul_(rho).addcmul_(delta, delta, value=1 - rho)
+                    tgt.add_(delta, alpha=-group["lr"])
+                    if master is not None:
+                        p.copy_(master.to(torch.bfloat16))
+                continue
+            desc, max_numel = self._group_desc(gi, params)
+            binding.fused_adadelta(
+                desc, len(params), max_numel, group["lr"], rho, eps,
+                group["weight_decay"],
             )
         return loss

@@ -34,7 +34,12 @@ def autolog(enable: bool = True) -> None:
     _autolog_enabled = enable
 
 
-def _make_optimizer(spec, params, lr: Optional[float] = None):
+# optimizer names with a fused, fp32-master kernel (ops/optim.py)
+_FUSED_NAMES = ("adam", "sgd", "adadelta")
+
+
+def _make_optimizer(spec, params, lr: Optional[float] = None,
+                    precision: str = "fp32"):
     if isinstance(spec, torch.optim.Optimizer):
         return spec
     from ..parallel.api import DistributedOptimizer
@@ -42,16 +47,25 @@ def _make_optimizer(spec, params, lr: Optional[float] = None):
     if isinstance(spec, DistributedOptimizer):
         return spec
     name = str(spec)
+    if precision == "bf16" and name.lower() not in _FUSED_NAMES:
+        # a stock optimizer would keep state and update in bf16 and round
+        # most small updates away
+        raise ValueError(
+            f"optimizer {spec!r} has no fp32-master kernel for precision="
+            "'bf16'; use one of 'Adam', 'SGD', 'Adadelta' or pass an "
+            "optimizer instance")
     lr = 1e-3 if lr is None else lr
     key = name.lower()
     params = list(params)
     # fused ddlw optimizers on GPU (K10); stock torch otherwise
     on_gpu = bool(params) and params[0].is_cuda
-    if on_gpu and key in ("adam", "sgd"):
-        from ..ops.optim import FusedAdam, FusedSGD
+    if on_gpu and key in _FUSED_NAMES:
+        from ..ops.optim import FusedAdadelta, FusedAdam, FusedSGD
 
         if key == "adam":
             return FusedAdam(params, lr=lr)
+        if key == "adadelta":
+            return FusedAdadelta(params, lr=lr)
         return FusedSGD(params, lr=lr, momentum=0.0)
     table = {
         "adam": torch.optim.Adam,
@@ -94,9 +108,28 @@ def _accuracy(logits, labels):
 
 
 class Model:
-    """Wraps an ``nn.Module`` with compile/fit/evaluate."""
+    """Wraps an ``nn.Module`` with compile/fit/evaluate.
 
-    def __init__(self, module: torch.nn.Module, device: Optional[torch.device] = None):
+    ``precision``:
+
+    - ``"fp32"`` (default): the module and the batches are used as given.
+    - ``"bf16"``: the state the hand-written kernels are gated on. Needs a
+      CUDA device. The module is moved there and ``ops.apply_bf16_policy``
+      applied here, before any optimizer can be built from the parameters;
+      every batch goes through ``ops.prepare_batch`` (uint8 N x H x W x C
+      from the loader is the fast door); ``compile`` with an optimizer name
+      gives an fp32-master fused optimizer; ``predict`` returns fp32 logits.
+    - ``"auto"``: ``"bf16"`` on a CUDA device with the kernel library
+      loadable, else ``"fp32"``.
+
+    The resolved value is ``model.precision``. Saving is unchanged: under
+    bf16 the conv and linear weights are stored as bf16; ``load_model``
+    rebuilds the module in fp32 and ``load_state_dict`` widens them exactly.
+    The policy is not persisted — pass ``precision`` again after loading.
+    """
+
+    def __init__(self, module: torch.nn.Module, device: Optional[torch.device] = None,
+                 precision: str = "fp32"):
         self.module = module
         if device is None:
             try:
@@ -104,6 +137,22 @@ class Model:
             except StopIteration:
                 device = torch.device("cpu")
         self.device = device
+        if precision not in ("fp32", "bf16", "auto"):
+            raise ValueError(
+                f"precision must be 'fp32', 'bf16' or 'auto', got {precision!r}")
+        on_cuda = torch.device(device).type == "cuda"
+        if precision == "auto":
+            from ..ops import has_lib
+
+            precision = "bf16" if on_cuda and has_lib() else "fp32"
+        elif precision == "bf16" and not on_cuda:
+            raise ValueError(
+                f"precision='bf16' needs a CUDA device, got {device}")
+        self.precision = precision
+        if precision == "bf16":
+            from ..ops.precision import apply_bf16_policy
+
+            self.module = apply_bf16_policy(module.to(device))
         self.optimizer = None
         self.loss_fn = sparse_categorical_crossentropy_from_logits
         self.metrics: Sequence[str] = ()
@@ -119,7 +168,8 @@ class Model:
         learning_rate: Optional[float] = None,
     ) -> "Model":
         trainable = [p for p in self.module.parameters() if p.requires_grad]
-        self.optimizer = _make_optimizer(optimizer, trainable, learning_rate)
+        self.optimizer = _make_optimizer(optimizer, trainable, learning_rate,
+                                         self.precision)
         if loss is not None:
             self.loss_fn = loss
         self.metrics = tuple(metrics)
@@ -129,6 +179,15 @@ class Model:
     def _move(self, x: torch.Tensor) -> torch.Tensor:
         return x.to(self.device, non_blocking=True) if x.device != self.device else x
 
+    def _images(self, x: torch.Tensor) -> torch.Tensor:
+        """Batch to the device and, under bf16, into the policy's layout."""
+        x = self._move(x)
+        if self.precision == "bf16":
+            from ..ops.precision import prepare_batch
+
+            x = prepare_batch(self.module, x)
+        return x
+
     def _forward_loss(self, images: torch.Tensor, labels: torch.Tensor):
         logits = self.module(images)
         loss = self.loss_fn(logits, labels)
@@ -136,7 +195,7 @@ class Model:
 
     def train_step(self, images: torch.Tensor, labels: torch.Tensor) -> Dict[str, float]:
         self.module.train()
-        images, labels = self._move(images), self._move(labels)
+        images, labels = self._images(images), self._move(labels)
         self.optimizer.zero_grad(set_to_none=True)
         logits, loss = self._forward_loss(images, labels)
         loss.backward()
@@ -149,7 +208,7 @@ class Model:
     @torch.no_grad()
     def eval_step(self, images: torch.Tensor, labels: torch.Tensor) -> Dict[str, float]:
         self.module.eval()
-        images, labels = self._move(images), self._move(labels)
+        images, labels = self._images(images), self._move(labels)
         logits, loss = self._forward_loss(images, labels)
         out = {"loss": float(loss)}
         if "accuracy" in self.metrics:
@@ -203,6 +262,7 @@ class Model:
                     "learning_rate": self.optimizer.param_groups[0]["lr"],
                     "epochs": epochs,
                     "steps_per_epoch": steps_per_epoch or -1,
+                    "precision": self.precision,
                 }
             )
 
@@ -298,5 +358,8 @@ class Model:
         self.module.eval()
         outs = []
         for i in range(0, len(images), batch_size):
-            outs.append(self.module(self._move(images[i : i + batch_size])).cpu())
+            logits = self.module(self._images(images[i : i + batch_size]))
+            if self.precision == "bf16":
+                logits = logits.float()  # on the device: numpy has no bf16
+            outs.append(logits.cpu())
         return torch.cat(outs)

@@ -5,10 +5,16 @@ Equivalent of ``Part 2 .../01_hyperopt_single_machine_model.py``: TPE over
 {optimizer, lr, dropout}, trials run concurrently by LocalTrials (each
 pinned to its own GPU when GPUs exist), child runs under a parent tracking
 run, best run found via search_runs, registered and promoted to Production.
+
+``--precision bf16`` (or ``auto`` on a GPU) runs every trial on the
+hand-written kernels; both optimizers of the space then keep fp32 master
+weights (``FusedAdam`` / ``FusedAdadelta``), so a small learning rate still
+trains. The default, ``fp32``, is the plain library path.
 """
 import os as _os, sys as _sys
 _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
 import argparse
+import functools
 import math
 
 import torch
@@ -26,9 +32,10 @@ BATCH_SIZE = 32
 IMG = 64
 
 
-def objective_function(params):
+def objective_function(params, precision="fp32"):
     """One trial (reference P2/01:133-181): rebuild datasets, train, return
-    {'loss': -accuracy, 'status': STATUS_OK}."""
+    {'loss': -accuracy, 'status': STATUS_OK}. Float batches under bf16 are
+    cast on the device by ``Model``."""
     setup()
     autolog()
     tbl = read_table("silver_train", columns=["content", "label_idx"])
@@ -43,7 +50,7 @@ def objective_function(params):
     module = build_model(IMG, IMG, 3, int(ys.max()) + 1, dropout=params["dropout"])
     if device:
         module = module.to(device)
-    model = Model(module, device=device)
+    model = Model(module, device=device, precision=precision)
     model.compile(optimizer=params["optimizer"], learning_rate=params["learning_rate"])
     with tracking.start_run(nested=True):
         model.fit(batches, epochs=2, verbose=0)
@@ -57,6 +64,8 @@ def main():
     ap.add_argument("--root", default=None)
     ap.add_argument("--max-evals", type=int, default=8)
     ap.add_argument("--parallelism", type=int, default=4)
+    ap.add_argument("--precision", choices=("fp32", "bf16", "auto"), default="fp32",
+                    help="bf16: the fused-kernel path (needs a GPU); auto: bf16 where it works")
     args = ap.parse_args()
     setup(root=args.root)
 
@@ -68,7 +77,7 @@ def main():
     tracking.set_experiment("hyperopt_single_machine")
     with tracking.start_run(run_name="hpo_parent") as parent:
         best = fmin(
-            objective_function,
+            functools.partial(objective_function, precision=args.precision),
             search_space,
             algo=tpe.suggest,
             max_evals=args.max_evals,

@@ -10,6 +10,11 @@ Equivalent of ``Part 2 .../03_pyfunc_distributed_inference.py``:
   that logs the img-params dict, the torch model, and the pyfunc bundle;
 - single-node predict on a few rows, then the predict-UDF fanned out across
   local GPU workers on 1000 rows (bounded by table size here).
+
+``--precision bf16`` (or ``auto`` on a GPU): the loader delivers uint8
+batches (``output="uint8"``), training runs under ``Model(precision=...)``,
+and the packaged predict-function decodes to uint8 and predicts through
+``Model(...).predict`` as well. The default, ``fp32``, is the plain path.
 """
 import os as _os, sys as _sys
 _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
@@ -43,9 +48,29 @@ class FlowerPyFunc(PythonModel):
         self.model = load_torch_model(context.artifacts["torch_model_path"])
         self.model.eval()
 
+    def _predict_policy(self, model_input, precision):
+        """uint8 decode + ``Model.predict`` under the trained precision;
+        ``None`` where that resolves to fp32 (no GPU)."""
+        from ddlw_amd.data.decode import decode_resize_u8
+
+        if not torch.cuda.is_available():
+            return None
+        if not hasattr(self, "_facade"):
+            self._facade = Model(self.model, torch.device("cuda:0"), precision=precision)
+        if self._facade.precision != "bf16":
+            return None
+        h, w = self.img_params["img_height"], self.img_params["img_width"]
+        u8 = torch.from_numpy(np.stack([decode_resize_u8(c, h, w) for c in model_input]))
+        return self._facade.predict(u8, batch_size=BATCH_SIZE)
+
     def predict(self, context, model_input):
         from ddlw_amd.data.preprocess import preprocess_pil
 
+        precision = self.img_params.get("precision", "fp32")
+        if precision != "fp32":
+            logits = self._predict_policy(model_input, precision)
+            if logits is not None:
+                return np.take(self.classes, logits.argmax(-1).numpy())
         h, w = self.img_params["img_height"], self.img_params["img_width"]
         arrs = np.stack([preprocess_pil(c, h, w) for c in model_input])
         x = torch.from_numpy(arrs).permute(0, 3, 1, 2).float()
@@ -60,7 +85,7 @@ class FlowerPyFunc(PythonModel):
         return np.take(self.classes, idx)
 
 
-def train_model_with_converter(data_cfg: DataCfg, epochs: int = 2):
+def train_model_with_converter(data_cfg: DataCfg, epochs: int = 2, precision: str = "fp32"):
     """Reference P2/03:253-377 (train + package)."""
     label_map = json.loads(
         (table_path("silver_train").parent / "label_to_idx.json").read_text()
@@ -74,25 +99,28 @@ def train_model_with_converter(data_cfg: DataCfg, epochs: int = 2):
             "num_classes": len(classes),
             "classes": classes,
         }
-        run.log_dict(img_params, "img_params_dict.json")
-
         device = torch.device("cuda:0") if torch.cuda.is_available() else None
         module = build_model(data_cfg.img_height, data_cfg.img_width,
                              data_cfg.img_channels, len(classes))
         if device:
             module = module.to(device)
-        model = Model(module, device=device)
+        model = Model(module, device=device, precision=precision)
         model.compile(optimizer="Adam", learning_rate=1e-3)
+        if model.precision != "fp32":
+            img_params["precision"] = model.precision
+        run.log_dict(img_params, "img_params_dict.json")
+        # under bf16 the loader ships bytes and the model's stem normalizes
+        loader_kw = {"output": "uint8"} if model.precision == "bf16" else {}
 
         conv_train = make_converter(str(table_path(data_cfg.train_table)))
         conv_val = make_converter(str(table_path(data_cfg.val_table)))
         steps = max(1, len(conv_train) // data_cfg.batch_size)
         with conv_train.make_torch_dataset(
             batch_size=data_cfg.batch_size, img_height=data_cfg.img_height,
-            img_width=data_cfg.img_width, device=device,
+            img_width=data_cfg.img_width, device=device, **loader_kw,
         ) as tds, conv_val.make_torch_dataset(
             batch_size=data_cfg.batch_size, img_height=data_cfg.img_height,
-            img_width=data_cfg.img_width, device=device,
+            img_width=data_cfg.img_width, device=device, **loader_kw,
         ) as vds:
             model.fit(
                 tds, steps_per_epoch=steps, epochs=epochs,
@@ -118,11 +146,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=None)
     ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--precision", choices=("fp32", "bf16", "auto"), default="fp32",
+                    help="bf16: the fused-kernel path (needs a GPU); auto: bf16 where it works")
     args = ap.parse_args()
     setup(root=args.root)
     tracking.set_experiment("pyfunc_inference")
     cfg = DataCfg(img_height=IMG, img_width=IMG, batch_size=32)
-    uri = train_model_with_converter(cfg)
+    uri = train_model_with_converter(cfg, precision=args.precision)
     print("pyfunc:", uri)
 
     rows = read_table("silver", columns=["content"]).column("content").to_pylist()
