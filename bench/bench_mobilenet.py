@@ -35,9 +35,10 @@ k = 13 and 3, default route vs ``DDLW_PW_TRAIN=0`` (the previous behaviour).
 Same protocol, same rule (``binding.pw_train_route`` holds the verdicts).
 
 The facade (``facade_head_step_u8``): the head-training step from a uint8
-batch through ``train.Model(precision="bf16")``, through ``Model(precision=
-"fp32")`` on the normalized fp32 batch, and as the hand loop — three
-contenders alternating. The optimizer (``adadelta_step_*``): one
+batch through ``train.Model(precision="bf16")`` with the metrics read back
+every step (``train_step``) and kept on the device (the ``fit``-path step),
+through ``Model(precision="fp32")`` on the normalized fp32 batch, and as the
+hand loop — four contenders alternating. The optimizer (``adadelta_step_*``): one
 ``FusedAdadelta`` step vs ``torch.optim.Adadelta(foreach=True)`` over the fp32
 trainable parameters of ``fine_tune_at=13`` and of the head alone; recorded
 only.
@@ -411,10 +412,14 @@ def _stats(samples: dict, B=None) -> dict:
 
 def bench_facade_step(B, dev, iters, rounds):
     """The head-training step of ``build_model(224, 224, 3, 5)`` from a uint8
-    batch, three ways, alternating: ``train.Model(precision="bf16")``
-    ("facade_bf16"), ``Model(precision="fp32")`` on the normalized fp32 NCHW
-    batch ("facade_fp32", what the examples run by default) and the hand loop
-    of ``bench_end_to_end_u8`` ("hand"). The claim: the bf16 median beats the
+    batch, four ways, alternating: ``train.Model(precision="bf16")``
+    ("facade_bf16", ``train_step``: loss and accuracy read back every step),
+    the same model's ``fit``-path step with the metrics on the device
+    ("facade_bf16_device"), ``Model(precision="fp32")`` on the normalized
+    fp32 NCHW batch ("facade_fp32") and the hand loop of
+    ``bench_end_to_end_u8`` ("hand"). The claims: the device-metrics median
+    beats the per-step median by more than the per-step spread
+    (``device_beats_per_step``), and the bf16 median beats the
     fp32 median by more than the fp32 spread (``bf16_beats_fp32``)."""
     from ddlw_amd.train import Model
 
@@ -439,13 +444,29 @@ def bench_facade_step(B, dev, iters, rounds):
         opt.step()
         return loss
 
+    # the step as ``fit`` issues it with the metrics on the device: nothing
+    # read back, the host held to RUN_AHEAD steps in front of the device
+    m16d = Model(build_model(224, 224, 3, 5), dev, precision="bf16")
+    m16d.compile("Adam", learning_rate=1e-3)
+    ahead = m16d._run_ahead()
+
+    def device_step():
+        m16d.train_step_async(u8, labels)
+        ahead.tick()
+
     s = time_interleaved({"facade_bf16": lambda: m16.train_step(u8, labels),
+                          "facade_bf16_device": device_step,
                           "facade_fp32": lambda: m32.train_step(x32, labels),
                           "hand": hand_step}, iters, rounds)
     rec = _stats(s, B)
     rec["bf16_beats_fp32"] = bool(
         rec["ms_facade_fp32"] - rec["ms_facade_bf16"] > rec["spread_facade_fp32"])
     rec["facade_minus_hand_ms"] = round(rec["ms_facade_bf16"] - rec["ms_hand"], 4)
+    # the routing rule for metrics_on_device=None: beat the per-step facade
+    # by more than that contender's spread
+    rec["device_beats_per_step"] = bool(
+        rec["ms_facade_bf16"] - rec["ms_facade_bf16_device"] > rec["spread_facade_bf16"])
+    rec["device_minus_hand_ms"] = round(rec["ms_facade_bf16_device"] - rec["ms_hand"], 4)
     return rec
 
 

@@ -16,6 +16,7 @@ from .layers import (
     MaxPool3x3s2,
     GlobalAvgPool2d,
     softmax_cross_entropy,
+    softmax_ce_metrics,
     normalize_u8_bf16,
 )
 from .optim import FusedSGD, FusedAdam, FusedAdadelta
@@ -31,6 +32,7 @@ __all__ = [
     "MaxPool3x3s2",
     "GlobalAvgPool2d",
     "softmax_cross_entropy",
+    "softmax_ce_metrics",
     "normalize_u8_bf16",
     "FusedSGD",
     "FusedAdam",

@@ -61,6 +61,8 @@ SIGNATURES = {
     "ddlw_dropout_bwd": (_I, [_P, _P, _P, _L, _F, _P]),
     "ddlw_argmax_rows": (_I, [_P, _P, _L, _I, _P]),
     "ddlw_accuracy": (_I, [_P, _P, _P, _L, _I, _P]),
+    "ddlw_ce_metrics_nblocks": (_I, [_I, _I, _P]),
+    "ddlw_ce_metrics": (_I, [_P] * 6 + [_I, _I, _F, _I, _P]),
     "ddlw_normalize_u8": (_I, [_P, _P, _L, _P]),
     # optim.hip
     "ddlw_fused_sgd": (_I, [_P, _I, _L, _F, _F, _F, _I, _P]),

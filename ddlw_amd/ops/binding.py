@@ -185,6 +185,46 @@ def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float):
     return loss_sum / B, dlogits
 
 
+@functools.lru_cache(maxsize=512)
+def ce_metrics_nblocks(B: int, K: int) -> int:
+    """Blocks ``ce_metrics`` walks [B, K] logits with: 1 is the single
+    launch, more is the rows kernel plus its finalize."""
+    return int(query("ce_metrics_nblocks", B, K, None))
+
+
+def ce_metrics(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float,
+               accum: Optional[torch.Tensor] = None, want_grad: bool = True):
+    """Loss, gradient and metrics of one step from the logits in one pass.
+    logits [B, K] bf16 or fp32, labels [B] (cast to int64). Returns
+    ``(step_out, dlogits)``: ``step_out`` fp32 [2] = (mean loss, accuracy);
+    ``dlogits`` = ``(softmax - onehot) * grad_scale`` in the logits' dtype,
+    ``None`` without ``want_grad``. ``accum``: fp64 [4] on the logits'
+    device, updated in place: += (mean loss, accuracy, 1, bad labels). A
+    label outside [0, K) gives zero loss and gradient and is counted there."""
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"ce_metrics: logits must be bf16 or fp32, got {logits.dtype}")
+    assert logits.dim() == 2, "ce_metrics: logits must be [B, K]"
+    B, K = logits.shape
+    assert labels.numel() == B, f"ce_metrics: {labels.numel()} labels for {B} rows"
+    assert labels.device == logits.device, "ce_metrics: labels on another device"
+    logits = logits.contiguous()
+    if labels.dtype != torch.int64:
+        labels = labels.to(torch.int64)
+    labels = labels.contiguous()
+    if accum is not None:
+        assert (accum.dtype == torch.float64 and accum.is_contiguous()
+                and accum.numel() == 4 and accum.device == logits.device), \
+            "ce_metrics: accum must be a contiguous fp64 [4] on the logits' device"
+    dev = logits.device
+    dlogits = torch.empty_like(logits) if want_grad else None
+    step_out = torch.empty(2, dtype=torch.float32, device=dev)
+    nb = ce_metrics_nblocks(B, K) if B > 0 and K > 0 else 1
+    part = torch.empty(3 * nb, dtype=torch.int32, device=dev) if nb > 1 else None
+    launch("ce_metrics", logits, labels, dlogits, step_out, accum, part, B, K,
+           grad_scale, 1 if logits.dtype == torch.bfloat16 else 0)
+    return step_out, dlogits
+
+
 def fused_sgd(chunk_desc: torch.Tensor, nchunks: int, max_numel: int, lr: float,
               momentum: float, weight_decay: float, first_step: bool):
     """chunk_desc: int64 device tensor [nchunks, 5] of

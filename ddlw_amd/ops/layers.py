@@ -313,6 +313,58 @@ def softmax_cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.T
     return F.cross_entropy(logits.float(), labels)
 
 
+class _SoftmaxCEMetricsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, accum):
+        step_out, dlogits = binding.ce_metrics(
+            logits, labels, 1.0 / logits.shape[0], accum,
+            want_grad=ctx.needs_input_grad[0])
+        if dlogits is not None:
+            ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(step_out)
+        return step_out[0], step_out
+
+    @staticmethod
+    def backward(ctx, dloss, _dstep):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * dloss, None, None
+
+
+def _softmax_ce_metrics_torch(logits, labels, accum):
+    """``softmax_ce_metrics`` in torch ops, bad labels and accumulators
+    included; the gradient is autograd's."""
+    lf = logits.float()
+    B, K = lf.shape
+    labels = labels.to(torch.int64)
+    ok = (labels >= 0) & (labels < K)
+    rows = F.cross_entropy(lf, torch.where(ok, labels, torch.zeros_like(labels)),
+                           reduction="none")
+    loss = torch.where(ok, rows, torch.zeros_like(rows)).sum() / B
+    with torch.no_grad():
+        correct = ((lf.argmax(-1) == labels) & ok).sum()
+        step_out = torch.stack([loss.detach(), correct.float() / B])
+        if accum is not None:
+            one = torch.ones((), dtype=torch.float64, device=accum.device)
+            accum += torch.stack([step_out[0].double(), step_out[1].double(), one,
+                                  (B - ok.sum()).double()])
+    return loss, step_out
+
+
+def softmax_ce_metrics(logits: torch.Tensor, labels: torch.Tensor,
+                       accum: Optional[torch.Tensor] = None):
+    """Sparse CE from bf16 or fp32 logits [B, K] together with the step's
+    metrics. Returns ``(loss, step_out)``: ``loss`` the fp32 0-dim mean,
+    differentiable (a bf16 gradient for bf16 logits); ``step_out`` fp32 [2] =
+    (mean loss, accuracy). ``accum``: fp64 [4], updated in place with
+    += (mean loss, accuracy, 1, labels outside [0, K)); such a label adds no
+    loss and no gradient and counts as wrong. One kernel and no host sync on
+    GPU; the same values from torch ops on CPU or under
+    ``DDLW_DISABLE_HIP_OPS=1``."""
+    if logits.is_cuda and not _hip_ops_disabled():
+        return _SoftmaxCEMetricsFn.apply(logits, labels, accum)
+    return _softmax_ce_metrics_torch(logits, labels, accum)
+
+
 # --------------------------------------------------------------------------- #
 # preprocess normalize (uint8 -> bf16 in [-1, 1])
 # --------------------------------------------------------------------------- #

@@ -34,6 +34,13 @@ def autolog(enable: bool = True) -> None:
     _autolog_enabled = enable
 
 
+# What ``metrics_on_device=None`` means where the device path is possible.
+# Off: on the head-training step the device path's median was 0.045 ms under
+# the per-step path's, inside that contender's spread of 0.379 ms, so the
+# routing rule does not keep it as the default (docs/KERNELS.md, "Benchmark:
+# the facade and the optimizer step"). ``metrics_on_device=True`` asks for it.
+_DEVICE_METRICS_DEFAULT = False
+
 # optimizer names with a fused, fp32-master kernel (ops/optim.py)
 _FUSED_NAMES = ("adam", "sgd", "adadelta")
 
@@ -107,6 +114,31 @@ def _accuracy(logits, labels):
     return (logits.argmax(-1) == labels).float().mean()
 
 
+class _RunAhead:
+    """Bound on how far the host runs ahead of the device when no step reads
+    anything back. ``tick()`` after a step records an event and waits for the
+    one recorded ``depth - 1`` steps before it, so when the next step is
+    issued at most ``depth`` steps are unfinished. The events are recorded
+    on ``device``'s current stream, whichever device is current, and are made
+    once: ``reset()`` starts a new loop on the same ring."""
+
+    def __init__(self, depth: int, device):
+        self.device = torch.device(device)
+        with torch.cuda.device(self.device):
+            self.events = [torch.cuda.Event() for _ in range(depth)]
+        self.n = 0
+
+    def reset(self) -> None:
+        self.n = 0
+
+    def tick(self) -> None:
+        d = len(self.events)
+        self.events[self.n % d].record(torch.cuda.current_stream(self.device))
+        self.n += 1
+        if self.n >= d:
+            self.events[self.n % d].synchronize()
+
+
 class Model:
     """Wraps an ``nn.Module`` with compile/fit/evaluate.
 
@@ -126,7 +158,18 @@ class Model:
     bf16 the conv and linear weights are stored as bf16; ``load_model``
     rebuilds the module in fp32 and ``load_state_dict`` widens them exactly.
     The policy is not persisted — pass ``precision`` again after loading.
+
+    ``RUN_AHEAD`` (2): with the metrics on the device no step reads anything
+    back, so nothing else stops the host from queueing a whole epoch of an
+    in-memory dataset. ``fit`` and ``evaluate`` let at most this many steps
+    be unfinished when they issue the next one. Two is the least that keeps
+    the device busy: one step runs while the host queues the one after it. A
+    deeper queue hides nothing more, because a step is queued no faster than
+    the launch rate that already bounds it, and it delays ``stop_training``,
+    an interrupt and the epoch's clock by as many steps.
     """
+
+    RUN_AHEAD = 2
 
     def __init__(self, module: torch.nn.Module, device: Optional[torch.device] = None,
                  precision: str = "fp32"):
@@ -158,6 +201,26 @@ class Model:
         self.metrics: Sequence[str] = ()
         self.stop_training = False
         self._steps_per_epoch: Optional[int] = None
+        self._train_metrics = None
+        self._eval_metrics = None
+        self._ahead = None
+
+    # the running sums of the ``*_step_async`` methods, made on first use
+    @property
+    def train_metrics(self):
+        if self._train_metrics is None:
+            from .metrics import DeviceMetrics
+
+            self._train_metrics = DeviceMetrics(self.device)
+        return self._train_metrics
+
+    @property
+    def eval_metrics(self):
+        if self._eval_metrics is None:
+            from .metrics import DeviceMetrics
+
+            self._eval_metrics = DeviceMetrics(self.device)
+        return self._eval_metrics
 
     # ------------------------------------------------------------------ #
     def compile(
@@ -215,6 +278,64 @@ class Model:
             out["accuracy"] = float(_accuracy(logits, labels))
         return out
 
+    def train_step_async(self, images: torch.Tensor, labels: torch.Tensor) -> None:
+        """``train_step`` with nothing read back: loss, gradient, accuracy
+        and the running sums come from one kernel (``train_metrics``), so the
+        call returns once the step is queued."""
+        self.module.train()
+        images, labels = self._images(images), self._move(labels)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.train_metrics.update(self.module(images), labels)
+        loss.backward()
+        self.optimizer.step()
+
+    @torch.no_grad()
+    def eval_step_async(self, images: torch.Tensor, labels: torch.Tensor) -> None:
+        """``eval_step`` with nothing read back (``eval_metrics``)."""
+        self.module.eval()
+        images, labels = self._images(images), self._move(labels)
+        self.eval_metrics.update(self.module(images), labels)
+
+    def _run_ahead(self) -> _RunAhead:
+        """This model's run-ahead bound, restarted for a new step loop."""
+        if self._ahead is None or len(self._ahead.events) != self.RUN_AHEAD:
+            self._ahead = _RunAhead(self.RUN_AHEAD, self.device)
+        self._ahead.reset()
+        return self._ahead
+
+    # ------------------------------------------------------------------ #
+    def _device_metrics_blocker(self, callbacks: Sequence[Callback]) -> Optional[str]:
+        """Why ``fit`` / ``evaluate`` cannot keep the metrics on the device,
+        or None if they can."""
+        from ..ops import has_lib
+        from ..ops.layers import _hip_ops_disabled
+
+        if torch.device(self.device).type != "cuda":
+            return f"the model is on {self.device}, not on a CUDA device"
+        if _hip_ops_disabled():
+            return "DDLW_DISABLE_HIP_OPS=1 switches the kernels off"
+        if not has_lib():
+            return "the kernel library is not loadable"
+        if self.loss_fn is not sparse_categorical_crossentropy_from_logits:
+            return "the loss is not the default sparse_categorical_crossentropy_from_logits"
+        extra = [m for m in self.metrics if m != "accuracy"]
+        if extra:
+            return f"metrics {extra} are not computed on the device (only 'accuracy')"
+        for cb in callbacks:
+            if type(cb).on_batch_end is not Callback.on_batch_end:
+                return (f"callback {type(cb).__name__} overrides on_batch_end "
+                        "and needs the logs of every step")
+        return None
+
+    def _use_device_metrics(self, flag: Optional[bool],
+                            callbacks: Sequence[Callback] = ()) -> bool:
+        if flag is False or (flag is None and not _DEVICE_METRICS_DEFAULT):
+            return False
+        why = self._device_metrics_blocker(callbacks)
+        if flag and why is not None:
+            raise ValueError(f"metrics_on_device=True, but {why}")
+        return why is None
+
     # ------------------------------------------------------------------ #
     def fit(
         self,
@@ -225,9 +346,22 @@ class Model:
         validation_steps: Optional[int] = None,
         callbacks: Sequence[Callback] = (),
         verbose: int = 1,
+        metrics_on_device: Optional[bool] = None,
     ) -> History:
+        """``metrics_on_device``: ``True`` keeps loss and accuracy on the
+        device and reads them once per epoch; it raises ``ValueError`` naming
+        the reason where that is not possible (it needs CUDA, the kernels
+        on, the default loss, no metric but accuracy and no callback that
+        overrides ``on_batch_end``). ``False`` reads them back every step.
+        ``None`` is auto: the device path where it is possible and
+        ``_DEVICE_METRICS_DEFAULT`` holds — which it does not as shipped,
+        the measured gain being inside the spread, so ``None`` is ``False``
+        today. The validation pass gets the same value and decides for
+        itself: it has no callbacks, so a callback that holds training on
+        the per-step path does not hold validation there."""
         if self.optimizer is None:
             raise RuntimeError("call compile() before fit()")
+        on_device = self._use_device_metrics(metrics_on_device, callbacks)
         # An infinite stream (Petastorm num_epochs=None semantics) with no
         # steps_per_epoch would never end an epoch — fail loudly instead
         # (Keras shares this footgun; we don't).
@@ -278,6 +412,9 @@ class Model:
             agg: Dict[str, float] = {}
             n = 0
             step = 0
+            if on_device:
+                self.train_metrics.reset()
+                ahead = self._run_ahead()
             while steps_per_epoch is None or step < steps_per_epoch:
                 with tracer.span(f"data[e{epoch}s{step}]", "data", tid=_api.rank()):
                     try:
@@ -293,6 +430,13 @@ class Model:
                             break
                 for cb in callbacks:
                     cb.on_batch_begin(step)
+                if on_device:
+                    # no callback here overrides on_batch_end: nothing to call
+                    with tracer.span(f"train_step[e{epoch}s{step}]", "step", tid=_api.rank()):
+                        self.train_step_async(images, labels)
+                    ahead.tick()
+                    step += 1
+                    continue
                 with tracer.span(f"train_step[e{epoch}s{step}]", "step", tid=_api.rank()):
                     logs = self.train_step(images, labels)
                 for cb in callbacks:
@@ -301,11 +445,15 @@ class Model:
                     agg[k] = agg.get(k, 0.0) + v
                 n += 1
                 step += 1
-            epoch_logs = {k: v / max(n, 1) for k, v in agg.items()}
+            if on_device:
+                epoch_logs = self.train_metrics.result(self.metrics)
+            else:
+                epoch_logs = {k: v / max(n, 1) for k, v in agg.items()}
 
             if validation_data is not None:
                 val_logs = self.evaluate(
-                    validation_data, steps=validation_steps, return_dict=True
+                    validation_data, steps=validation_steps, return_dict=True,
+                    metrics_on_device=metrics_on_device,
                 )
                 epoch_logs.update({f"val_{k}": v for k, v in val_logs.items()})
 
@@ -333,22 +481,36 @@ class Model:
         data: Iterable,
         steps: Optional[int] = None,
         return_dict: bool = False,
+        metrics_on_device: Optional[bool] = None,
     ):
+        """``metrics_on_device``: as for ``fit``; one readback per call."""
+        on_device = self._use_device_metrics(metrics_on_device)
         agg: Dict[str, float] = {}
         n = 0
         it = iter(data)
         step = 0
+        if on_device:
+            self.eval_metrics.reset()
+            ahead = self._run_ahead()
         while steps is None or step < steps:
             try:
                 images, labels = next(it)
             except StopIteration:
                 break
+            if on_device:
+                self.eval_step_async(images, labels)
+                ahead.tick()
+                step += 1
+                continue
             logs = self.eval_step(images, labels)
             for k, v in logs.items():
                 agg[k] = agg.get(k, 0.0) + v
             n += 1
             step += 1
-        out = {k: v / max(n, 1) for k, v in agg.items()}
+        if on_device:
+            out = self.eval_metrics.result(self.metrics)
+        else:
+            out = {k: v / max(n, 1) for k, v in agg.items()}
         if return_dict:
             return out
         return [out.get("loss", 0.0)] + [out[m] for m in self.metrics if m in out]
