@@ -85,6 +85,7 @@ SIGNATURES = {
                             + [POINTER(c_long), POINTER(c_long), POINTER(c_int), _P]),
     # conv_wgrad.hip
     "ddlw_conv_wgrad": (_I, [_P] * 5 + [_I] * 12 + [_P]),
+    "ddlw_conv_wgrad3x3": (_I, [_P] * 5 + [_I] * 10 + [_P]),
     # conv_stem.hip
     "ddlw_stem_repack": (_I, [_P, _P, _I, _I, _I, _P]),
     "ddlw_conv_stem": (_I, [_P] * 4 + [_I] * 8 + [_P, _P, _I, _P]),

@@ -301,3 +301,287 @@ DDLW_EXPORT int ddlw_conv_wgrad(const void* dy, const void* x, const void* zpage
                      (const float*)slab, (bf16_t*)dw, elems, split);
   DDLW_CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------------------
+// Tap-fused 3x3 / stride 1 / pad 1 weight gradient.
+//
+// k_conv_wgrad runs one block per tap: nine blocks stage the same dy tile and
+// nine shifted copies of x. Here one block owns a (64 k, 64 c) tile and a
+// slice of output rows and produces all nine taps: 9 x (2x2) accumulator
+// fragments per wave (144 registers). dy is staged once per step and its
+// fragments are read from LDS once for the nine taps.
+//
+// Rows. Every output row is padded to PW m (PW = 8/16/32/64 >= Wo), so a 32-m
+// MFMA group is made of whole rows and whole [4][16] blocks. The tap shift in
+// s moves m by one, which a transpose read (four consecutive m out of one
+// 128-B block) cannot address, so x is staged as three images per input row,
+// one per s, from source addresses shifted by s-1. The shift in r is a whole
+// row: the image of input row h serves output rows h-1, h and h+1, so the
+// row images live in an LDS ring (slot = row & (NR-1)) and every input row is
+// staged once per s.
+//
+// Image borders. Rows are numbered v = n*(H+1) + h + 1: one GAP row in front
+// of every image. A gap row is staged from the zero page, in dy and in x, so
+// the tap above row 0 and the tap below row H-1 read zeros and never the
+// neighbouring image. Columns: m >= Wo of a padded row and taps left of
+// column 0 / right of column W-1 are staged from the zero page as well. A
+// slice [g0, g1) of output rows walks v from v(g0) to v(g1-1) in steps of RPS
+// rows; x row v(g0)-1 (the halo above, a gap row when the slice starts an
+// image) and x row v(g1-1)+1 are staged too, dy rows outside the slice and x
+// rows past the lower halo come from the zero page.
+//
+// Row image: [c16][PW/4 blocks of [4 m][16 c]], within every unit of
+// EB = min(PW/4, 8) blocks the even-m blocks before the odd-m blocks, so the
+// two transpose reads of a fragment each take all their blocks of one row
+// from one contiguous run. For PW < 32 the four 16-lane groups of a read
+// gather from different rows (ring slots); the slot stride of PW = 8 is
+// padded by 128 B so that two neighbouring rows fall on different banks.
+template <int PW>
+__global__ __launch_bounds__(256) void k_conv_wgrad3x3(
+    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+    const bf16_t* __restrict__ zpage,
+    float* __restrict__ slab,  // [SPLIT][K][9*C]
+    int N, int H, int W_, int C, int K,
+    int rows_q, int rows_rem,  // slice sizes: q rows, the first rem one more
+    unsigned long long magic_h, unsigned shift_h) {
+  constexpr int RPS = PW >= 32 ? 1 : 32 / PW;  // output rows per step
+  constexpr int SM = RPS * PW;                 // m per step
+  constexpr int MG = SM / 32;                  // 32-m groups per step
+  constexpr int NR = 4 * RPS;                  // ring slots (>= 2*RPS + 2)
+  constexpr int BPR = PW / 4;                  // blocks per row per c16
+  constexpr int EB = BPR < 8 ? BPR : 8;        // blocks per even/odd unit
+  constexpr int PP = PW / 8;                   // 1-KiB pieces per row image
+  constexpr int ROWIMG = PW * 64;              // elements per (row, s) image
+  constexpr int SLOT = 3 * ROWIMG + (PW == 8 ? 64 : 0);
+  constexpr int DYIMG = SM * 64;
+  constexpr unsigned ODD = EB / 2 * 128;       // bytes from even to odd block
+  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * DYIMG + NR * SLOT];
+  bf16_t* const xring = smem + 2 * DYIMG;
+
+  const int ctiles = C / 64;
+  const int tile_k = blockIdx.x / ctiles;
+  const int tile_c = blockIdx.x % ctiles;
+  const int sp = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 1, wc2 = wave & 1;
+
+  // slice [g0, g1) of the N*H output rows -> virtual rows [v0, v1)
+  const int g0 = sp * rows_q + (sp < rows_rem ? sp : rows_rem);
+  const int gl = g0 + rows_q + (sp < rows_rem ? 1 : 0) - 1;
+  const int n0 = (int)mdiv((unsigned)g0, magic_h, shift_h);
+  const int n1 = (int)mdiv((unsigned)gl, magic_h, shift_h);
+  const int ho0 = g0 - n0 * H;
+  const int L = (n1 - n0) * (H + 1) + (gl - n1 * H) - ho0 + 1;  // v1 - v0
+  const int nsteps = (L + RPS - 1) / RPS;
+
+  // staging lane geometry inside a 1-KiB piece (8 blocks of 8 16-B chunks)
+  const int s_pos = lane >> 3;
+  const int s_mr = (lane >> 1) & 3;
+  const int s_koff = (lane & 1) * 8;
+
+  // next row to stage, as (image, row + 1 within the image, row - (v0 - 1));
+  // x starts at the halo row v0 - 1, dy at v0
+  int xn = n0, xhp = ho0, xrel = 0;
+  int dn = n0, dhp = ho0 + 1, drel = 1;
+
+  auto stage_x = [&](auto count) {
+    constexpr int COUNT = decltype(count)::value;
+    constexpr int TOTAL = COUNT * 3 * PP;
+    #pragma unroll
+    for (int i = 0; i < (TOTAL + 3) / 4; ++i) {
+      const int idx = i * 4 + wave;
+      if (TOTAL % 4 != 0 && idx >= TOTAL) break;
+      const int ric = idx / (3 * PP);
+      const int s = (idx / PP) % 3;
+      const int p = idx % PP;
+      int n = xn, hp = xhp + ric;
+      while (hp > H) { hp -= H + 1; ++n; }
+      const int rel = xrel + ric;
+      const bool rowok = hp >= 1 && rel <= L + 1 && n < N;
+      // chunk position -> (c16, block of the row): even blocks come first
+      const int P = p * 8 + s_pos;
+      const int c16 = P / BPR;
+      const int e = P % EB;
+      const int b = e < EB / 2 ? 2 * e : 2 * (e - EB / 2) + 1;
+      const int wo = ((P % BPR) / EB * EB + b) * 4 + s_mr;
+      const int w = wo + s - 1;
+      const bool ok = rowok && wo < W_ && w >= 0 && w < W_;
+      const bf16_t* src =
+          ok ? x + (((long)n * H + (hp - 1)) * W_ + w) * C + tile_c * 64 +
+                   c16 * 16 + s_koff
+             : zpage;
+      bf16_t* dst = xring + (rel & (NR - 1)) * SLOT + s * ROWIMG + p * 512;
+      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)src,
+                                       (LDS_AS void*)dst, 16, 0, 0);
+    }
+    xhp += COUNT;
+    while (xhp > H) { xhp -= H + 1; ++xn; }
+    xrel += COUNT;
+  };
+
+  auto stage_dy = [&](int buf) {
+    bf16_t* ldy = smem + buf * DYIMG;
+    #pragma unroll
+    for (int i = 0; i < MG; ++i) {  // 4*MG pieces (k16, 32-m group)
+      const int idx = i * 4 + wave;
+      const int k16 = idx / MG, g = idx % MG;
+      const int b = s_pos < 4 ? 2 * s_pos : 2 * (s_pos - 4) + 1;
+      const int ms = g * 32 + b * 4 + s_mr;  // m within the step
+      const int ri = ms / PW, wo = ms % PW;
+      int n = dn, hp = dhp + ri;
+      while (hp > H) { hp -= H + 1; ++n; }
+      const bool ok = hp >= 1 && drel + ri <= L && wo < W_;
+      const bf16_t* src =
+          ok ? dy + (((long)n * H + (hp - 1)) * W_ + wo) * K + tile_k * 64 +
+                   k16 * 16 + s_koff
+             : zpage;
+      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)src,
+                                       (LDS_AS void*)(ldy + idx * 512), 16, 0, 0);
+    }
+    dhp += RPS;
+    while (dhp > H) { dhp -= H + 1; ++dn; }
+    drel += RPS;
+  };
+
+  f32x4_v acc[9][2][2];
+  #pragma unroll
+  for (int t9 = 0; t9 < 9; ++t9)
+    #pragma unroll
+    for (int a = 0; a < 2; ++a)
+      #pragma unroll
+      for (int b = 0; b < 2; ++b) acc[t9][a][b] = {0.f, 0.f, 0.f, 0.f};
+
+  // fragment-read lane geometry: 16-lane group q reads m = 8q .. 8q+7 of the
+  // 32-m group, i.e. blocks 2q (first read) and 2q+1 (second) of padded row
+  // (8q)/PW
+  const int f_q = lane >> 4;
+  const int f_ri = (f_q * 8) / PW;
+  const int f_blk = ((f_q * 8) % PW) / 8;  // even block's place among evens
+  const unsigned f_x = lds_u32(xring) + (unsigned)(wc2 * 2 * BPR + f_blk) * 128 +
+                       (lane & 15) * 8;
+  const unsigned f_dy = lds_u32(smem) + (unsigned)(wr * 2 * MG) * 1024 + lane * 8;
+
+  stage_x(std::integral_constant<int, 2>{});
+  stage_x(std::integral_constant<int, RPS>{});
+  stage_dy(0);
+  __syncthreads();
+
+  int cur = 0;
+  for (int t = 0; t < nsteps; ++t) {
+    if (t + 1 < nsteps) {
+      stage_dy(cur ^ 1);
+      stage_x(std::integral_constant<int, RPS>{});
+    }
+    // ring slot of input row (out row + r - 1) for this lane's padded row
+    unsigned xa[3];
+    #pragma unroll
+    for (int r = 0; r < 3; ++r)
+      xa[r] = f_x + (unsigned)((t * RPS + f_ri + r) & (NR - 1)) * (SLOT * 2);
+    const unsigned da = f_dy + (unsigned)cur * (DYIMG * 2);
+    #pragma unroll
+    for (int g = 0; g < MG; ++g) {
+      tr64_t fk[2][2], fx[2][2][2];
+      #pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const unsigned addr = da + (a * MG + g) * 1024;
+        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fk[a][0]) : "v"(addr));
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:512"
+                     : "=v"(fk[a][1]) : "v"(addr));
+      }
+      auto load_tap = [&](int tap, int fb) {
+        const int r = tap / 3, s = tap % 3;
+        #pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const unsigned addr =
+              xa[r] + (unsigned)(s * ROWIMG * 2 + b * BPR * 128 + g * 1024);
+          asm volatile("ds_read_b64_tr_b16 %0, %1"
+                       : "=v"(fx[fb][b][0]) : "v"(addr));
+          asm volatile("ds_read_b64_tr_b16 %0, %1"
+                       : "=v"(fx[fb][b][1]) : "v"(addr + ODD));
+        }
+      };
+      load_tap(0, 0);
+      #pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        // the next tap's fragments load behind this tap's MFMAs
+        if (tap + 1 < 9) load_tap(tap + 1, (tap + 1) & 1);
+        #pragma unroll
+        for (int a = 0; a < 2; ++a)
+          #pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            union { struct { tr64_t lo, hi; } p; bf16x8_v v; } fa, fb;
+            fa.p.lo = fk[a][0]; fa.p.hi = fk[a][1];
+            fb.p.lo = fx[tap & 1][b][0]; fb.p.hi = fx[tap & 1][b][1];
+            acc[tap][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                fa.v, fb.v, acc[tap][a][b], 0, 0, 0);
+          }
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // epilogue: D map col=lane&15 (c), row=(lane>>4)*4+q (k); fp32 slab write
+  const long RSC = 9l * C;
+  float* out = slab + (long)sp * K * RSC;
+  const int c0 = tile_c * 64 + wc2 * 32 + (lane & 15);
+  const int k0 = tile_k * 64 + wr * 32 + (lane >> 4) * 4;
+  #pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+    #pragma unroll
+    for (int a = 0; a < 2; ++a)
+      #pragma unroll
+      for (int b = 0; b < 2; ++b)
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+          out[(long)(k0 + a * 16 + q) * RSC + tap * C + c0 + b * 16] =
+              acc[tap][a][b][q];
+}
+
+// 3x3 / stride 1 / pad 1 only (Ho = H, Wo = W_); `split` slices of whole
+// output rows, sizes differing by at most one (conv_gemm.wgrad3x3_slices)
+DDLW_EXPORT int ddlw_conv_wgrad3x3(const void* dy, const void* x,
+                                   const void* zpage, void* slab, void* dw,
+                                   int N, int H, int W_, int C, int K, int R,
+                                   int S, int stride, int pad, int split,
+                                   void* stream) {
+  const char* who = "conv_wgrad3x3";
+  if (R != 3 || S != 3) return ddlw_fail(who, "R and S must be 3");
+  if (stride != 1) return ddlw_fail(who, "stride must be 1");
+  if (pad != 1) return ddlw_fail(who, "pad must be 1");
+  if (C % 64 != 0 || K % 64 != 0)
+    return ddlw_fail(who, "C and K must be multiples of 64");
+  if (N < 1 || H < 1 || W_ < 1 || W_ > 64)
+    return ddlw_fail(who, "width must be 1..64");
+  const long rows = (long)N * H;
+  if ((long)N * (H + 1) * W_ >= (1ll << 31))
+    return ddlw_fail(who, "N*(H+1)*W >= 2^31 unsupported");
+  if (split < 1 || split > rows || split > 65535)
+    return ddlw_fail(who, "split must be 1..min(N*H, 65535)");
+  unsigned long long mg_h;
+  unsigned sh_h;
+  make_magic((unsigned)H, &mg_h, &sh_h);
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid((K / 64) * (C / 64), split);
+  const int pw = W_ <= 8 ? 8 : W_ <= 16 ? 16 : W_ <= 32 ? 32 : 64;
+  with_int<8, 16, 32, 64>(pw, [&](auto PWc) {
+    hipLaunchKernelGGL((k_conv_wgrad3x3<decltype(PWc)::value>), grid,
+                       dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x,
+                       (const bf16_t*)zpage, (float*)slab, N, H, W_, C, K,
+                       (int)(rows / split), (int)(rows % split), mg_h, sh_h);
+  });
+  {
+    hipError_t err_ = hipGetLastError();
+    if (err_ != hipSuccess) { ddlw_set_error(hipGetErrorString(err_)); return 1; }
+  }
+  long elems = (long)K * 9 * C;
+  long g = cdiv(elems, 32);
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((int)g), dim3(256), 0, st,
+                     (const float*)slab, (bf16_t*)dw, elems, split);
+  DDLW_CHECK_LAUNCH();
+}
