@@ -179,8 +179,14 @@ struct S2Quad {
 // MASKED: acc_mask is honoured. A template flag so that the unmasked
 // instantiations keep exactly the code (and the fp32 summation order of the
 // BN partials) they had.
+// PF > 0 (bounce epilogue only): the epilogue's side reads — acc, acc_mask,
+// bnb_x, bnb_mask — are issued PF store-loop iterations ahead of their use,
+// and with ACC_EARLY the add is taken from a coalesced fp32 bounce instead
+// of the per-element gather. Lane -> (row, chunk) mapping, the ascending-row
+// order of each lane's partial sums and the shuffle tree are those of PF = 0,
+// so both give the same bits. A template flag for the same reason as MASKED.
 template <int BM, int BN, bool EPI_LDS, int BUFS, bool M32EN = true,
-          bool ACC_EARLY = false, bool MASKED = false>
+          bool ACC_EARLY = false, bool MASKED = false, int PF = 0>
 __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
     bf16_t* __restrict__ y, const bf16_t* __restrict__ zpage,
@@ -529,7 +535,53 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
   // own instantiation (the launcher picks it for acc + bnb at T > 4): as a
   // runtime branch it cost the single-K-step tiles a wave of occupancy.
   constexpr bool acc_early = ACC_EARLY && !M32;
-  if constexpr (M32) {
+  // PF > 0: the side reads of iteration `it` of the store loop below are
+  // issued PF iterations ahead (the first PF groups right here, before the
+  // accumulators go to LDS: the addresses depend on the tile indices only).
+  // Each load keeps the predicate of the load it replaces. F32B: the early
+  // add is taken from an fp32 bounce of the accumulators (two halves of
+  // WM/2 rows, the wave's own LDS region) with the same coalesced mapping,
+  // not from the per-element gather.
+  constexpr bool F32B = acc_early && PF > 0;
+  constexpr int NIT = WM / (64 / (WN / 8));  // store-loop iterations
+  constexpr int PFD = PF < NIT ? PF : NIT;
+  constexpr int PFN = PF > 0 ? NIT : 1;
+  uint4 pf_a[PFN], pf_x[PFN];
+  unsigned pf_am[PFN], pf_xm[PFN];
+  auto pf_issue = [&](int it) {
+    const int row = it * (64 / (WN / 8)) + lane / (WN / 8);
+    const long m = tile_m * BM + wr * WM + row;
+    const int jb = tile_n * BN + wc * WN + (lane % (WN / 8)) * 8;
+    if (m < M && jb + 8 <= K) {
+      const long o = out_row(m) * K + jb;
+      if (accp && (!acc_early || F32B)) {
+        pf_a[it] = *reinterpret_cast<const uint4*>(accp + o);
+        if constexpr (MASKED) pf_am[it] = acc_mask[o >> 3];
+      }
+      if (bn_ps && bnb_x) {
+        pf_x[it] = *reinterpret_cast<const uint4*>(bnb_x + o);
+        pf_xm[it] = bnb_mask ? bnb_mask[o >> 3] : 0xffu;
+      }
+    }
+  };
+  // the per-channel bnb constants go first: loads return in order, and the
+  // first store-loop iteration needs them
+  float pf_bnm[PF > 0 ? 8 : 1], pf_bnr[PF > 0 ? 8 : 1];
+  if constexpr (PF > 0) {
+    if (bn_ps && bnb_x) {
+      #pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        int j = tile_n * BN + wc * WN + (lane % (WN / 8)) * 8 + e;
+        pf_bnm[e] = (j < K) ? bnb_mean[j] : 0.f;
+        pf_bnr[e] = (j < K) ? bnb_rstd[j] : 0.f;
+      }
+    }
+    #pragma unroll
+    for (int it = 0; it < PFD; ++it) pf_issue(it);
+  }
+  if constexpr (F32B) {
+    // written half by half inside the store loop
+  } else if constexpr (M32) {
     #pragma unroll
     for (int mi = 0; mi < MF2; ++mi)
       #pragma unroll
@@ -600,20 +652,86 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
   if (bn_ps && bnb_x) {
     #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      int j = j_base + e;
-      bnm8[e] = (j < K) ? bnb_mean[j] : 0.f;
-      bnr8[e] = (j < K) ? bnb_rstd[j] : 0.f;
+      if constexpr (PF > 0) {
+        bnm8[e] = pf_bnm[e];
+        bnr8[e] = pf_bnr[e];
+      } else {
+        int j = j_base + e;
+        bnm8[e] = (j < K) ? bnb_mean[j] : 0.f;
+        bnr8[e] = (j < K) ? bnb_rstd[j] : 0.f;
+      }
     }
   }
   #pragma unroll
   for (int it = 0; it < WM / RPI; ++it) {
     const int row = it * RPI + e_row;
     const long m = m_base + row;
-    uint4 val = *reinterpret_cast<const uint4*>(lC + row * WNP + e_ch * 8);
+    if constexpr (PF > 0) {
+      if (it + PFD < NIT) pf_issue(it + PFD);
+    }
+    uint4 val;
+    float vf[F32B ? 8 : 1];
+    if constexpr (F32B) {
+      constexpr int WNF = WN + 4;   // fp32 row pitch: half a region fits
+      constexpr int HIT = NIT / 2;  // iterations per half of WM/2 rows
+      static_assert((WM / 2) * WNF * 4 <= WM * WNP * 2, "fp32 half fits");
+      float* lF = reinterpret_cast<float*>(lC);
+      if (it % HIT == 0) {
+        #pragma unroll
+        for (int mi = 0; mi < MF / 2; ++mi)
+          #pragma unroll
+          for (int ni = 0; ni < NF; ++ni)
+            #pragma unroll
+            for (int q = 0; q < 4; ++q)
+              lF[(mi * 16 + d_row0 + q) * WNF + ni * 16 + d_col] =
+                  acc[(it / HIT) * (MF / 2) + mi][ni][q];
+      }
+      const float* src = lF + (row - (it / HIT) * (WM / 2)) * WNF + e_ch * 8;
+      const float4 lo = *reinterpret_cast<const float4*>(src);
+      const float4 hi = *reinterpret_cast<const float4*>(src + 4);
+      vf[0] = lo.x; vf[1] = lo.y; vf[2] = lo.z; vf[3] = lo.w;
+      vf[4] = hi.x; vf[5] = hi.y; vf[6] = hi.z; vf[7] = hi.w;
+    } else {
+      val = *reinterpret_cast<const uint4*>(lC + row * WNP + e_ch * 8);
+    }
+    if constexpr (PF > 0) {
+      // One drain once the last group is out and this iteration's LDS
+      // traffic is issued (vmcnt(0); expcnt, lgkmcnt left alone). The
+      // groups sit behind lane predicates, so without it the compiler
+      // cannot know they have landed on every path and puts a vmcnt(0) —
+      // which also waits for the previous iteration's store — in front of
+      // each iteration.
+      if (it == (NIT - PFD > 0 ? NIT - PFD - 1 : 0))
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
     if (m < M) {
       const long orow = out_row(m);
       if (j_base + 8 <= K) {
-        if (!MASKED && ep_scale) {
+        if constexpr (F32B) {
+          // early add, coalesced: fp32 accumulator + (masked) acc chunk,
+          // one rounding — the arithmetic of the gather it replaces
+          uint4 a = pf_a[it];
+          unsigned mb = 0xffu;
+          if constexpr (MASKED) mb = pf_am[it];
+          const unsigned* aw = &a.x;
+          unsigned* vw = &val.x;
+          #pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            float alo = b2f((bf16_t)(aw[d] & 0xffff));
+            float ahi = b2f((bf16_t)(aw[d] >> 16));
+            if (!((mb >> (2 * d)) & 1)) alo = 0.f;
+            if (!((mb >> (2 * d + 1)) & 1)) ahi = 0.f;
+            vw[d] = (unsigned)f2b(vf[2 * d] + alo) |
+                    ((unsigned)f2b(vf[2 * d + 1] + ahi) << 16);
+          }
+          // From here on val is to the compiler what the LDS read is in the
+          // other instantiations: an opaque bf16 chunk. Without this the
+          // fast-math reassociation of the dgamma product below sees
+          // through to the fp32 sum and picks another multiplication order
+          // (measured: the partials then differ in the last bit).
+          asm volatile("" : "+v"(val.x), "+v"(val.y), "+v"(val.z), "+v"(val.w));
+          *reinterpret_cast<uint4*>(y + orow * K + j_base) = val;
+        } else if (!MASKED && ep_scale) {
           uint4 a{0, 0, 0, 0};
           if (accp)
             a = *reinterpret_cast<const uint4*>(accp + orow * K + j_base);
@@ -634,11 +752,19 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
           // accumulate: coalesced uint4 read of the add-input at the same
           // address, pairwise bf16 add in fp32 (matches the engine's
           // bf16+bf16 add numerics)
-          uint4 a = *reinterpret_cast<const uint4*>(accp + orow * K + j_base);
+          uint4 a;
+          if constexpr (PF > 0)
+            a = pf_a[it];
+          else
+            a = *reinterpret_cast<const uint4*>(accp + orow * K + j_base);
           if constexpr (MASKED) {
             // one byte covers this 8-channel chunk; a cleared bit turns
             // its bf16 half into +0.0
-            const unsigned mb = acc_mask[(orow * K + j_base) >> 3];
+            unsigned mb;
+            if constexpr (PF > 0)
+              mb = pf_am[it];
+            else
+              mb = acc_mask[(orow * K + j_base) >> 3];
             auto keep = [&](int e) -> unsigned {
               return (((mb >> e) & 1) ? 0xffffu : 0u) |
                      (((mb >> (e + 1)) & 1) ? 0xffff0000u : 0u);
@@ -665,8 +791,15 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
           if (bnb_x) {
             // BN-BWD partials: masked dy and dy*xhat (j_base is 8-aligned
             // so the mask byte covers exactly this chunk)
-            unsigned mb = bnb_mask ? bnb_mask[(orow * K + j_base) >> 3] : 0xffu;
-            uint4 xv = *reinterpret_cast<const uint4*>(bnb_x + orow * K + j_base);
+            unsigned mb;
+            uint4 xv;
+            if constexpr (PF > 0) {
+              mb = pf_xm[it];
+              xv = pf_x[it];
+            } else {
+              mb = bnb_mask ? bnb_mask[(orow * K + j_base) >> 3] : 0xffu;
+              xv = *reinterpret_cast<const uint4*>(bnb_x + orow * K + j_base);
+            }
             #pragma unroll
             for (int e = 0; e < 8; ++e) {
               unsigned wd = (e < 2) ? val.x : (e < 4) ? val.y : (e < 6) ? val.z : val.w;
@@ -689,7 +822,10 @@ __global__ __launch_bounds__(256) void k_conv_fwd_igemm(
             }
           }
         }
-      } else {
+      } else if constexpr (PF == 0) {
+        // (the PF instantiations run only where K % 8 == 0 — the launcher
+        // sees to it — so a chunk is whole or dead and this scalar tail,
+        // whose loads would put a wait into every iteration, is left out)
         // static component extraction (a reinterpret pointer into `val`
         // forces the register to scratch — rule 20)
         #pragma unroll
@@ -1067,6 +1203,12 @@ static TilePick pick_tile(long M, int K, int C, int T, bool want_stats,
   return p;
 }
 
+// DDLW_EPI_PREFETCH: 0 -> off, anything else or unset -> on
+static bool epi_prefetch_lever() {
+  const char* e = getenv("DDLW_EPI_PREFETCH");
+  return !(e && e[0] == '0');
+}
+
 DDLW_EXPORT long ddlw_conv_fwd_nparts(int N, int C, int K, int Ho, int Wo,
                                       int R, int S, int bnb) {
   long M = (long)N * Ho * Wo;
@@ -1140,7 +1282,56 @@ DDLW_EXPORT int ddlw_conv_fwd_igemm(const void* x, const void* w, void* y,
 #undef WIDE_LAUNCH
     DDLW_CHECK_LAUNCH();
   }
-  if (acc && want_bnb && T > 4) {
+  // Bounce epilogue that carries acc or bnb: side reads prefetched (the PF
+  // instantiations), same bits. DDLW_EPI_PREFETCH=0 restores the in-order
+  // instantiations below; read per call. They have no scalar tail for a
+  // partial 8-channel chunk, so K % 8 != 0 stays in order too, and so does
+  // the BN = 32 tile (K < 64: no layer of the models here, not measured).
+  // Depth 7 of the 8 store-loop
+  // iterations (the 8th group goes out in iteration 0; narrower tiles have
+  // 4 or 2 iterations, all in flight): the most the 128x128 tiles hold at
+  // 2 waves/SIMD (188 VGPR + 64..68 AGPR). The two-buffer tiles sit at 2
+  // waves by LDS anyway; the one-buffer tile gives up its third wave for it
+  // (one iteration ahead already takes 108 + 68 registers, over the 168 that
+  // three waves leave).
+  const bool early = acc && want_bnb && T > 4;
+  // The unmasked early add stays in order as well: its PF instantiation is
+  // 1.9x faster (285 -> 148 us at 14x14 512 -> 1024, B = 256) but the
+  // compiler multiplies the dgamma term f * (x - mean) * rstd in another
+  // order there (fast-math), and the partials differ in the last bit.
+  if (epi_prefetch_lever() && (acc || want_bnb) && !want_ep && !p.m32 &&
+      K % 8 == 0 && p.bn >= 64 && (p.epi_lds || early) &&
+      !(early && !acc_mask)) {
+    with_int<128, 64>(p.bn, [&](auto BN) {
+      with_bool(acc_mask != nullptr, [&](auto MSK) {
+        long grid = cdiv(M, 128) * cdiv(K, decltype(BN)::value);
+#define PF_LAUNCH(BUFS_, EARLY_)                                               \
+        hipLaunchKernelGGL(                                                    \
+            (k_conv_fwd_igemm<128, decltype(BN)::value, true, BUFS_, false,    \
+                              EARLY_, decltype(MSK)::value, 7>),               \
+            dim3((int)grid), dim3(256), 0, st, (const bf16_t*)x,               \
+            (const bf16_t*)w, (bf16_t*)y, (const bf16_t*)zpage, N, H, W_, C,   \
+            K, Ho, Wo, R, S, stride, pad, (int)grid, oH, oW, oS, mg_wo, sh_wo, \
+            mg_ho, sh_ho, (const bf16_t*)acc, (const unsigned char*)acc_mask,  \
+            (float*)bn_ps, (float*)bn_pq, (const bf16_t*)bnb_x,                \
+            (const unsigned char*)bnb_mask, (const float*)bnb_mean,            \
+            (const float*)bnb_rstd, nullptr, nullptr, 0)
+        if constexpr (decltype(MSK)::value) {
+          if (early) {
+            PF_LAUNCH(2, true);
+            return;
+          }
+        }
+        if (p.bufs == 2)
+          PF_LAUNCH(2, false);
+        else
+          PF_LAUNCH(1, false);
+#undef PF_LAUNCH
+      });
+    });
+    DDLW_CHECK_LAUNCH();
+  }
+  if (early) {
     // acc + bnb on a shape whose own route is the direct epilogue: the
     // bounce epilogue with the early (fp32) accumulate, so dx is the same
     // with and without the reduce partials
