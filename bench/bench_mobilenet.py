@@ -34,6 +34,13 @@ and one training step of ``build_model(224, 224, 3, 5, fine_tune_at=k)`` for
 k = 13 and 3, default route vs ``DDLW_PW_TRAIN=0`` (the previous behaviour).
 Same protocol, same rule (``binding.pw_train_route`` holds the verdicts).
 
+The training stem from uint8 (``stem_u8_train`` row, ``scratch_step_u8``):
+``_StemU8BnActFn`` forward + backward vs ``normalize_u8_input`` + the
+``Conv2d`` module + ``BatchNormAct2d`` in training mode, and one from-scratch
+step (``fine_tune_at=0``) from a uint8 batch, ``DDLW_STEM_U8_TRAIN=1`` vs
+``=0``. Same alternation, same rule (``mbconv.stem_u8_train_enabled`` holds
+the verdict); ``--only-stem-u8-train`` runs just these two.
+
 The facade (``facade_head_step_u8``): the head-training step from a uint8
 batch through ``train.Model(precision="bf16")`` with the metrics read back
 every step (``train_step``) and kept on the device (the ``fit``-path step),
@@ -279,12 +286,18 @@ def bench_pointwise_train(B, H, C, K, dev, iters, rounds):
 
 
 def _with_env(name, value, fn):
+    """fn with ``name=value`` in the environment; what was there before is
+    put back afterwards."""
     def run():
+        before = os.environ.get(name)
         os.environ[name] = value
         try:
             return fn()
         finally:
-            os.environ.pop(name, None)
+            if before is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = before
     return run
 
 
@@ -318,6 +331,87 @@ def bench_finetune_step(B, k, dev, iters, rounds):
     rec = _verdict(s)
     rec["ms_forced"] = round(statistics.median(s["forced"]), 4)
     rec["spread_forced"] = round(max(s["forced"]) - min(s["forced"]), 4)
+    rec["spread_fused"] = round(max(s["fused"]) - min(s["fused"]), 4)
+    for name in ("fused", "unfused"):
+        rec[f"img_s_{name}"] = round(B / rec[f"ms_{name}"] * 1e3, 1)
+    # acceptance: not slower than the contender by more than its spread
+    rec["not_slower"] = bool(rec["ms_fused"] - rec["ms_unfused"] <= rec["spread_unfused"])
+    return rec
+
+
+def bench_stem_u8_train(B, size, dev, iters, rounds):
+    """The TRAINING stem from a uint8 batch, forward + backward of the stage:
+    ``_StemU8BnActFn`` on a marked net ("fused") against the path an unmarked
+    net takes ("unfused"): ``normalize_u8_input``, the 3->32 ``Conv2d``
+    module, ``BatchNormAct2d`` in training mode."""
+    from ddlw_amd.models.mobilenet_v2 import MobileNetV2
+    from ddlw_amd.ops import mbconv
+
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, size, size, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    net = apply_bf16_policy(MobileNetV2().to(dev)).train()
+    net.features = net.features[:3]              # the stage alone
+    conv, bn = net.features[0], net.features[1]
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.2, 0.2)
+    Ho = (size - 1) // 2 + 1
+    gout = _cl(torch.randn(B, 32, Ho, Ho, device=dev).to(torch.bfloat16))
+    params = (conv.weight, bn.weight, bn.bias)
+
+    def run(forward):
+        for p in params:
+            p.grad = None
+        y = forward()
+        y.backward(gout)
+        return y, [p.grad for p in params]
+
+    def fused():
+        return run(lambda: mbconv.stem_u8_train_forward(net, x))
+
+    def unfused():
+        return run(lambda: bn(conv(mbconv.normalize_u8_input(x, conv.weight))))
+
+    assert _with_env("DDLW_STEM_U8_TRAIN", "1",
+                     lambda: mbconv.stem_u8_train_fusable(net, x))()
+    (yf, gf), (yu, gu) = fused(), unfused()
+    err = ((yf.float() - yu.float()).abs().max() / (yu.float().abs().max() + 1e-6)).item()
+    err_dw = ((gf[0].float() - gu[0].float()).norm() / (gu[0].float().norm() + 1e-30)).item()
+    s = time_interleaved({"fused": fused, "unfused": unfused}, iters, rounds)
+    rec = _verdict(s)
+    rec["spread_fused"] = round(max(s["fused"]) - min(s["fused"]), 4)
+    # GB/s over the conv's own I/O (the bytes twice, y written, dy read); the
+    # BN passes of the stage move more
+    bytes_io = 2 * 3.0 * B * size * size + 2 * 2.0 * B * Ho * Ho * 32
+    return {"kind": "stem_u8_tr", "shape": f"n{B}_h{size}_c3_k32_s2",
+            "rel_err_vs_unfused": round(err, 5), "rel_l2_dw_vs_unfused": round(err_dw, 5),
+            **rec, "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)}
+
+
+def bench_scratch_step_u8(B, dev, iters, rounds):
+    """One from-scratch training step (``fine_tune_at=0``: every layer
+    trains) on a uint8 batch under the bf16 policy: the marked stem on the
+    uint8 stem kernels ("fused", ``DDLW_STEM_U8_TRAIN=1``) vs
+    ``DDLW_STEM_U8_TRAIN=0`` ("unfused"), alternating in one process."""
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    labels = torch.randint(0, 5, (B,), device=dev)
+    model = apply_bf16_policy(build_model(224, 224, 3, 5, fine_tune_at=0).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    s = time_interleaved({"fused": _with_env("DDLW_STEM_U8_TRAIN", "1", step),
+                          "unfused": _with_env("DDLW_STEM_U8_TRAIN", "0", step)},
+                         iters, rounds)
+    rec = _verdict(s)
     rec["spread_fused"] = round(max(s["fused"]) - min(s["fused"]), 4)
     for name in ("fused", "unfused"):
         rec[f"img_s_{name}"] = round(B / rec[f"ms_{name}"] * 1e3, 1)
@@ -517,6 +611,8 @@ def main():
                     help="skip the fine-tuning sections")
     ap.add_argument("--skip-facade", action="store_true",
                     help="skip the Model-facade and Adadelta-step sections")
+    ap.add_argument("--only-stem-u8-train", action="store_true",
+                    help="run only the training-stem-from-uint8 stage and step")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -524,8 +620,18 @@ def main():
         sys.exit("bench_mobilenet: no GPU (timings are only meaningful on the device)")
     dev = torch.device("cuda:0")
     B = args.batch
+    if args.only_stem_u8_train:
+        args.skip_layers = args.skip_e2e = args.skip_facade = True
     layers = []
     train_layers = []
+    stem_train = []
+    if args.only_stem_u8_train or (not args.skip_layers and not args.skip_train):
+        # the stage is a fraction of a millisecond: ten times the calls per
+        # round, so a round is a ~0.1 s window and not a few milliseconds
+        rec = bench_stem_u8_train(B, 224, dev, args.iters * 10, args.rounds)
+        stem_train.append(rec)
+        print(json.dumps(rec), flush=True)
+        _table(stem_train)
     if not args.skip_layers and not args.skip_train:
         seen = []
         for (H, C, K, _act, _res) in layer_shapes(224)[0]:
@@ -559,6 +665,10 @@ def main():
             r = bench_finetune_step(B, k, dev, args.e2e_iters, args.rounds)
             finetune[f"finetune_step_at_{k}"] = r
             print(json.dumps({f"finetune_step_at_{k}": r}), flush=True)
+    if args.only_stem_u8_train or (not args.skip_e2e and not args.skip_train):
+        r = bench_scratch_step_u8(B, dev, args.e2e_iters, args.rounds)
+        finetune["scratch_step_u8"] = r
+        print(json.dumps({"scratch_step_u8": r}), flush=True)
     e2e = ({} if args.skip_e2e or args.skip_frozen
            else bench_end_to_end(B, dev, args.e2e_iters, args.rounds))
     if e2e:
@@ -577,7 +687,8 @@ def main():
               f"unfused {r['ms_unfused']:.3f} ms ({r['img_s_unfused']} img/s)  "
               f"spread {r['spread_unfused']:.3f}  speedup {r['speedup']}")
     report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers,
-              "train_layers": train_layers, "stem_u8": stem, **finetune, **e2e, **facade}
+              "train_layers": train_layers, "stem_u8": stem,
+              "stem_u8_train": stem_train, **finetune, **e2e, **facade}
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(report, indent=2))
@@ -592,6 +703,9 @@ def main():
     if stem:
         summary["stem_u8"] = {k: stem[0][k] for k in ("ms_fused", "ms_unfused",
                                                       "spread_unfused", "speedup", "keep")}
+    if stem_train:
+        summary["stem_u8_train"] = {k: stem_train[0][k] for k in (
+            "ms_fused", "ms_unfused", "spread_unfused", "speedup", "keep")}
     for name, r in {**finetune, **e2e}.items():
         summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
                                            "img_s_unfused", "speedup")}

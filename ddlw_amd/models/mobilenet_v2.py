@@ -26,7 +26,9 @@ Input: a float batch, or the ``torch.uint8`` N x C x H x W batch over NHWC
 memory (``u8_nhwc.permute(0, 3, 1, 2)``) that the decode pool and the H2D ring
 deliver — ``preprocess_input`` (``x / 127.5 - 1``) then belongs to the model,
 and on the frozen bf16 route it is fused with the stem conv, its BN and ReLU6
-into one kernel (``MobileNetV2.stem_entry``, ``ops/mbconv.py``).
+into one kernel (``MobileNetV2.stem_entry``, ``ops/mbconv.py``). A training
+stem marked by ``enable_u8_train_stem`` (the bf16 policy does) can run from the
+bytes as well: ``DDLW_STEM_U8_TRAIN=1``, off by default (docs/KERNELS.md).
 
 No pretrained weights exist in this offline environment, so the base is
 randomly initialised (documented deviation; the benchmark configs use
@@ -127,6 +129,14 @@ class MobileNetV2(nn.Module):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
+    def enable_u8_train_stem(self, flag: bool = True) -> None:
+        """Opt the stem in to (or out of) the training-mode uint8 kernels:
+        the mark ``u8_train`` on ``features[0]``, an instance attribute like
+        ``Conv2d.pw_train`` (no parameter, buffer or state_dict key, kept by
+        ``deepcopy``, not saved). ``ops.precision.apply_bf16_policy`` sets it;
+        an unmarked net routes exactly as before."""
+        self.features[0].u8_train = bool(flag)
+
     def stem_entry(self, x: torch.Tensor, frozen_stem: bool = True):
         """The one entry for a batch, used by ``forward`` and by
         ``FrozenBase``'s split forward: returns ``(h, start)`` and the caller
@@ -136,11 +146,25 @@ class MobileNetV2(nn.Module):
         ``preprocess_input`` belongs to the model: when the stem is frozen
         (``frozen_stem``) and ``mbconv.stem_u8_fusable`` holds, normalize +
         stem conv + BN + ReLU6 run as one kernel and ``start = 3``; otherwise
-        the batch is normalized once and ``start = 0``."""
+        the batch is normalized once and ``start = 0``.
+
+        A stem marked by ``enable_u8_train_stem`` adds two routes, both
+        decided by the caller's grad mode: a TRAINING stem
+        (``mbconv.stem_u8_train_fusable``) runs on the stage Function of the
+        uint8 stem kernels, ``start = 3``, and the normalized batch is never
+        written; and a trainable stem that is merely evaluated (eval mode
+        under no-grad: validation during ``fit``) takes the fused frozen
+        kernel like a frozen one, since its BN uses the running statistics."""
         if x.dtype != torch.uint8:
             return x, 0
-        if frozen_stem and mbconv.stem_u8_fusable(self, x):
-            return mbconv.stem_u8_forward(self, x), 3
+        if mbconv.stem_u8_train_fusable(self, x):
+            return mbconv.stem_u8_train_forward(self, x), 3
+        # a trainable stem evaluated under no-grad: the fused kernel, on the
+        # live weight and BN tensors (nothing cached: they are being trained)
+        live = (not frozen_stem and getattr(self.features[0], "u8_train", False)
+                and not torch.is_grad_enabled())
+        if (frozen_stem or live) and mbconv.stem_u8_fusable(self, x):
+            return mbconv.stem_u8_forward(self, x, fresh=live), 3
         with torch.no_grad():
             return mbconv.normalize_u8_input(x, self.features[0].weight), 0
 
@@ -232,11 +256,17 @@ class FrozenBase(nn.Module):
                 return self.base(x)
         feats = self.base.features
         start = 0
+        if x.dtype == torch.uint8:
+            if self._split >= 3:
+                # frozen stem: the fused kernel
+                with torch.no_grad():
+                    x, start = self.base.stem_entry(x, frozen_stem=True)
+            else:
+                # a trainable stem gets the normalized batch and its modules,
+                # or, marked, the uint8 stem kernels as the caller's grad
+                # mode says (``stem_entry``); it normalizes under no_grad
+                x, start = self.base.stem_entry(x, frozen_stem=False)
         with torch.no_grad():
-            if x.dtype == torch.uint8:
-                # the fused stem only where the stem is frozen (split >= 3);
-                # a trainable stem gets the normalized batch and its modules
-                x, start = self.base.stem_entry(x, frozen_stem=self._split >= 3)
             for m in feats[start: self._split]:
                 x = m(x)
         for m in feats[max(start, self._split):]:

@@ -91,6 +91,10 @@ SIGNATURES = {
     "ddlw_conv_stem": (_I, [_P] * 4 + [_I] * 8 + [_P, _P, _I, _P]),
     "ddlw_stem_wgrad": (_I, [_P] * 5 + [_I] * 7 + [_P]),
     "ddlw_stem3_u8_fwd_ep": (_I, [_P] * 5 + [_I] * 6 + [_P]),
+    "ddlw_stem3_u8_nparts": (_I, [_L, _P]),
+    "ddlw_stem3_u8_fwd_stats": (_I, [_P] * 5 + [_I] * 6 + [_P]),
+    "ddlw_stem3_u8_wgrad_nparts": (_I, [_L, _P]),
+    "ddlw_stem3_u8_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
 }
 
 

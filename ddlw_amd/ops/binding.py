@@ -403,6 +403,72 @@ def stem3_u8_fwd_ep(x_u8: torch.Tensor, weight: torch.Tensor,
     return y
 
 
+@functools.lru_cache(maxsize=64)
+def _stem3_u8_nparts(rows: int) -> int:
+    return int(query("stem3_u8_nparts", rows, None))
+
+
+@functools.lru_cache(maxsize=64)
+def _stem3_u8_wgrad_nparts(rows: int) -> int:
+    return int(query("stem3_u8_wgrad_nparts", rows, None))
+
+
+def stem3_u8_fwd_stats(x_u8: torch.Tensor, weight: torch.Tensor,
+                       wp: Optional[torch.Tensor] = None):
+    """Training forward of the MobileNetV2 stem on a uint8 image batch:
+    ``conv3x3_s2_p1(x/127.5 - 1)`` raw (no scale, bias or activation) with
+    the BatchNorm statistics of its output from the epilogue. Returns ``(y,
+    part_sum, part_sumsq, nparts)``: y bf16 [N,32,Ho,Wo] channels_last,
+    bit-equal to ``stem3_u8_fwd_ep(x_u8, weight)``; the partials fp32
+    ``[nparts, 32]``, sums over the bf16 ``y``, for ``bn_finalize_parts``.
+    Arguments as ``stem3_u8_fwd_ep``'s."""
+    assert x_u8.is_cuda and weight.device == x_u8.device, "stem3_u8_fwd_stats: need one GPU"
+    assert x_u8.dtype == torch.uint8, f"stem3_u8_fwd_stats: need uint8, got {x_u8.dtype}"
+    assert x_u8.dim() == 4 and x_u8.is_contiguous(memory_format=torch.channels_last), \
+        "stem3_u8_fwd_stats: need a channels_last [N,C,H,W] batch"
+    n, c, h, w = x_u8.shape
+    K = weight.shape[0]
+    assert weight.shape[1] == c, f"stem3_u8_fwd_stats: x has {c} channels, weight {weight.shape[1]}"
+    if wp is None:
+        wp = stem3_pack_weight(weight)
+    assert (wp.dtype == torch.bfloat16 and wp.is_contiguous() and wp.device == x_u8.device
+            and tuple(wp.shape) == (K, -(-9 * c // 32) * 32)), "stem3_u8_fwd_stats: wp"
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    y = torch.empty((n, K, ho, wo), dtype=torch.bfloat16, device=x_u8.device,
+                    memory_format=torch.channels_last)
+    nparts = _stem3_u8_nparts(n * ho * wo)
+    both = torch.empty(2, max(nparts, 1), K, dtype=torch.float32, device=x_u8.device)
+    ps, pq = both[0, :nparts], both[1, :nparts]
+    launch("stem3_u8_fwd_stats", x_u8, wp, y, both[0], both[1], nparts, n, h, w, c, K)
+    return y, ps, pq, nparts
+
+
+def stem3_u8_wgrad(x_u8: torch.Tensor, dy: torch.Tensor, weight_shape) -> torch.Tensor:
+    """Weight gradient of the MobileNetV2 stem from the uint8 image batch,
+    fp32 [32,3,3,3]: ``dW[k][c][r][s] = sum dy[n][k][ho][wo] *
+    xn[n][c][2ho-1+r][2wo-1+s]`` with ``xn`` the ``normalize_u8_bf16`` value
+    gathered from the bytes (zero padding in normalized space). dy bf16
+    [N,32,Ho,Wo] channels_last. Two launches (per-block partials, then a
+    fixed-order sum): no atomics, bit-reproducible."""
+    assert x_u8.is_cuda and dy.device == x_u8.device, "stem3_u8_wgrad: need one GPU"
+    assert x_u8.dtype == torch.uint8, f"stem3_u8_wgrad: need uint8, got {x_u8.dtype}"
+    assert x_u8.dim() == 4 and x_u8.is_contiguous(memory_format=torch.channels_last), \
+        "stem3_u8_wgrad: need a channels_last [N,C,H,W] batch"
+    n, c, h, w = x_u8.shape
+    K, wc, r, s = weight_shape
+    assert wc == c, f"stem3_u8_wgrad: x has {c} channels, weight {wc}"
+    assert (r, s) == (3, 3), "stem3_u8_wgrad: 3x3 only"
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    assert tuple(dy.shape) == (n, K, ho, wo), \
+        f"stem3_u8_wgrad: dy is {tuple(dy.shape)}, the output is {(n, K, ho, wo)}"
+    nparts = _stem3_u8_wgrad_nparts(n * ho * wo)
+    part = torch.empty(max(nparts, 1), K, r * s * c, dtype=torch.float32,
+                       device=x_u8.device)
+    dw = torch.empty((K, c, r, s), dtype=torch.float32, device=x_u8.device)
+    launch("stem3_u8_wgrad", x_u8, _nhwc(dy), part, dw, nparts, n, h, w, c, K)
+    return dw
+
+
 # ---- pointwise conv, training path ---------------------------------------- #
 
 

@@ -118,9 +118,15 @@ class Conv2d(nn.Conv2d):
 
     ``pw_train``: opt-in mark a model sets on its 1x1 convs (an instance
     attribute, not a parameter or buffer) to train them on the pointwise
-    MFMA kernels; unmarked convs keep the routing below."""
+    MFMA kernels; unmarked convs keep the routing below.
+
+    ``u8_train``: the same kind of mark on a MobileNetV2 stem conv
+    (``MobileNetV2.enable_u8_train_stem``): a training stem takes a uint8
+    batch on the fused stem kernels (``ops/mbconv.py``). This forward never
+    reads it."""
 
     pw_train = False
+    u8_train = False
 
     def pw_trainable(self) -> bool:
         """A marked 1x1 stride-1 pad-0 conv of a shape the pointwise

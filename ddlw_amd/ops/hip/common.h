@@ -45,6 +45,22 @@ __device__ __forceinline__ float warp_reduce_max(float v) {
   return v;
 }
 
+// Sum over the 16 lanes of a DPP row (lane & 15 = the 16 rows of an MFMA
+// fragment, or 16 pixels): rotate by 8, 4, 2, 1 within the row. Every lane
+// ends with the total, added in an order that depends on nothing but the lane.
+template <int CTRL>
+__device__ __forceinline__ float row_ror_add(float v) {
+  const int i = __float_as_int(v);
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float row_sum16(float v) {
+  v = row_ror_add<0x128>(v);  // row_ror:8
+  v = row_ror_add<0x124>(v);  // row_ror:4
+  v = row_ror_add<0x122>(v);  // row_ror:2
+  return row_ror_add<0x121>(v);  // row_ror:1
+}
+
 // 8 consecutive fp32 (a per-channel table slice) as two 16-byte loads
 __device__ __forceinline__ void load8f(const float* __restrict__ p, float (&v)[8]) {
   const float4 a = *reinterpret_cast<const float4*>(p);
@@ -85,6 +101,16 @@ static inline int grid_1d(long work, int block = 256, int cap = 2048) {
       return 1;                                                                \
     }                                                                          \
     return 0;                                                                  \
+  } while (0)
+
+// between two launches of one export: return 1 on a launch error, else go on
+#define DDLW_CHECK_LAUNCH_OR_RETURN()                                         \
+  do {                                                                         \
+    hipError_t err_ = hipGetLastError();                                       \
+    if (err_ != hipSuccess) {                                                  \
+      ddlw_set_error(hipGetErrorString(err_));                                 \
+      return 1;                                                                \
+    }                                                                          \
   } while (0)
 
 void ddlw_set_error(const char* msg);

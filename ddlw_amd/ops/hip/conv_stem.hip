@@ -461,10 +461,7 @@ DDLW_EXPORT int ddlw_stem_wgrad(const void* dy, const void* x4,
                      (const bf16_t*)dy, (const bf16_t*)x4,
                      (const bf16_t*)zpage, (float*)slab, N, H, Wp, K, Ho, Wo,
                      2, 3, split, m_per_split, mg_wo, sh_wo, mg_ho, sh_ho);
-  {
-    hipError_t err_ = hipGetLastError();
-    if (err_ != hipSuccess) { ddlw_set_error(hipGetErrorString(err_)); return 1; }
-  }
+  DDLW_CHECK_LAUNCH_OR_RETURN();
   long elems = (long)K * 256;
   long g = (elems + 31) / 32;
   hipLaunchKernelGGL(k_wgrad_reduce, dim3((int)g), dim3(256), 0, st,
@@ -513,14 +510,78 @@ DDLW_EXPORT int ddlw_stem_wgrad(const void* dy, const void* x4,
 #define ST3_PIXEL 16               // the pixel itself: m < M
 #define ST3_NEVER 32               // a pad slot of the reduction (kk >= 27)
 
+// The uint8 gather, shared by every stem-u8 kernel (forward, forward with
+// statistics, weight gradient) ---------------------------------------------
+// The image geometry a kernel passes down, with the magic divisors of Wo, Ho.
+struct St3Geom {
+  int M, H, W, Ho, Wo;
+  unsigned long long magic_wo, magic_ho;
+  unsigned shift_wo, shift_ho;
+};
+
+// Taps kk = 8g .. 8g+7 of the reduction: byte offset from the window's centre
+// pixel, and what each needs of its pixel's window.
+__device__ __forceinline__ void st3_taps(int g, int W, int (&off)[8], int (&need)[8]) {
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int kk = g * 8 + e;
+    const int r = kk / 9, j = kk - 9 * r;  // j = 3s + c: byte in the window row
+    off[e] = (r - 1) * 3 * W + j - 3;
+    need[e] = ST3_PIXEL | (r == 0 ? ST3_TOP : 0) | (r == 2 ? ST3_BOT : 0) |
+              (j < 3 ? ST3_LEFT : 0) | (j >= 6 ? ST3_RIGHT : 0) |
+              (kk >= 27 ? ST3_NEVER : 0);
+  }
+}
+
+// Output pixel m: what its window has, and its centre pixel (2ho, 2wo), which
+// always lies inside the image. A pixel past M takes pixel M-1's (valid)
+// address and has no ST3_PIXEL, so every tap of it is zeroed.
+__device__ __forceinline__ int st3_pixel(const unsigned char* __restrict__ x,
+                                         const St3Geom& g, int m,
+                                         const unsigned char*& ctr) {
+  const unsigned mu = (unsigned)(m < g.M ? m : g.M - 1);
+  const unsigned q1 = mdiv(mu, g.magic_wo, g.shift_wo);       // n*Ho + ho
+  const int wo = (int)(mu - q1 * (unsigned)g.Wo);
+  const unsigned n_u = mdiv(q1, g.magic_ho, g.shift_ho);
+  const int ho = (int)(q1 - n_u * (unsigned)g.Ho);
+  // 2ho <= H-1 and 2wo <= W-1, and N*H*W*3 < 2^31
+  ctr = x + (((int)n_u * g.H + 2 * ho) * g.W + 2 * wo) * 3;
+  return (m < g.M ? ST3_PIXEL : 0) | (ho > 0 ? ST3_TOP : 0) |
+         (2 * ho + 1 < g.H ? ST3_BOT : 0) | (wo > 0 ? ST3_LEFT : 0) |
+         (2 * wo + 1 < g.W ? ST3_RIGHT : 0);
+}
+
+// One tap's byte: a tap the window does not have loads the centre byte.
+__device__ __forceinline__ unsigned char st3_byte(const unsigned char* ctr,
+                                                  int off, int need, int have) {
+  return ctr[(need & ~have) == 0 ? off : 0];
+}
+
+// ... and its value: k_normalize_u8's bf16, or 0 for a tap the window lacks
+// (zero padding in normalized space).
+__device__ __forceinline__ bf16_t st3_value(unsigned char byte, int need, int have) {
+  const float v = (float)byte * (1.f / 127.5f) - 1.f;
+  return f2b((need & ~have) == 0 ? v : 0.f);
+}
+
+// Forward. STATS = false: the frozen stem with the folded-BN epilogue.
+// STATS = true: the training forward — y is the raw conv output (no scale,
+// bias or activation) and block b also writes the BatchNorm statistics of its
+// 128 pixels, psum[b][32] = sum of y, psq[b][32] = sum of y^2 (fp32, the
+// layout k_bn_finalize / k_bn_parts_fold take). As in k_pw_conv_stats the
+// sums run over the bf16-ROUNDED outputs, and no sum is masked: a pixel past
+// M has every tap zeroed, so its accumulators are exactly 0. No atomics: a
+// lane folds its 2 pixels, a DPP row sum folds the 16 lanes, the 4 waves meet
+// once in LDS and are added in wave order.
+template <bool STATS>
 __global__ __launch_bounds__(256) void k_stem3_u8(
     const unsigned char* __restrict__ x,   // [N][H][W][3]
     const bf16_t* __restrict__ wp,         // [32][32]
     bf16_t* __restrict__ y,                // [M][32]
     const float* __restrict__ scale, const float* __restrict__ bias, int act,
-    int M, int H, int W, int Ho, int Wo,
-    unsigned long long magic_wo, unsigned shift_wo,
-    unsigned long long magic_ho, unsigned shift_ho) {
+    float* __restrict__ psum, float* __restrict__ psq,   // [gridDim.x][32]
+    St3Geom geo) {
+  const int M = geo.M;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int l15 = lane & 15;
@@ -529,15 +590,7 @@ __global__ __launch_bounds__(256) void k_stem3_u8(
 
   // the lane's 8 taps: byte offset from the centre pixel, and what they need
   int off[8], need[8];
-  #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int kk = lg * 8 + e;
-    const int r = kk / 9, j = kk - 9 * r;  // j = 3s + c: byte in the window row
-    off[e] = (r - 1) * 3 * W + j - 3;
-    need[e] = ST3_PIXEL | (r == 0 ? ST3_TOP : 0) | (r == 2 ? ST3_BOT : 0) |
-              (j < 3 ? ST3_LEFT : 0) | (j >= 6 ? ST3_RIGHT : 0) |
-              (kk >= 27 ? ST3_NEVER : 0);
-  }
+  st3_taps(lg, geo.W, off, need);
 
   union { uint4 u; s_bf16x8_v v; } fw[2], fx[ST3_MR];
   #pragma unroll
@@ -548,25 +601,12 @@ __global__ __launch_bounds__(256) void k_stem3_u8(
 
   #pragma unroll
   for (int mi = 0; mi < ST3_MR; ++mi) {
-    const int m = m0 + mi * 16 + l15;
-    const unsigned mu = (unsigned)(m < M ? m : M - 1);
-    const unsigned q1 = mdiv(mu, magic_wo, shift_wo);       // n*Ho + ho
-    const int wo = (int)(mu - q1 * (unsigned)Wo);
-    const unsigned n_u = mdiv(q1, magic_ho, shift_ho);
-    const int ho = (int)(q1 - n_u * (unsigned)Ho);
-    const int have = (m < M ? ST3_PIXEL : 0) | (ho > 0 ? ST3_TOP : 0) |
-                     (2 * ho + 1 < H ? ST3_BOT : 0) | (wo > 0 ? ST3_LEFT : 0) |
-                     (2 * wo + 1 < W ? ST3_RIGHT : 0);
-    // centre pixel (2ho, 2wo): 2ho <= H-1 and 2wo <= W-1, and N*H*W*3 < 2^31
-    const unsigned char* ctr =
-        x + (((int)n_u * H + 2 * ho) * W + 2 * wo) * 3;
+    const unsigned char* ctr;
+    const int have = st3_pixel(x, geo, m0 + mi * 16 + l15, ctr);
     bf16x8 o;
     #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const bool ok = (need[e] & ~have) == 0;
-      const float v = (float)ctr[ok ? off[e] : 0] * (1.f / 127.5f) - 1.f;
-      o.h[e] = f2b(ok ? v : 0.f);
-    }
+    for (int e = 0; e < 8; ++e)
+      o.h[e] = st3_value(st3_byte(ctr, off[e], need[e], have), need[e], have);
     fx[mi].u = o.v;
   }
 
@@ -579,6 +619,51 @@ __global__ __launch_bounds__(256) void k_stem3_u8(
           fw[f].v, fx[mi].v, s_f32x4_v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 
   // epilogue: lane (lg, l15) holds channels 8lg .. 8lg+7 of pixel m0 + mi*16 + l15
+  if constexpr (STATS) {
+    __shared__ __attribute__((aligned(16))) float red[2][ST3_WAVES][32];
+    float s[8], q[8];
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
+    #pragma unroll
+    for (int mi = 0; mi < ST3_MR; ++mi) {
+      const int m = m0 + mi * 16 + l15;
+      bf16x8 o;
+      #pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        o.h[e] = f2b(acc[e >> 2][mi][e & 3]);
+        const float r = b2f(o.h[e]);
+        s[e] += r;
+        q[e] += r * r;
+      }
+      if (m < M) *reinterpret_cast<uint4*>(y + (long)m * 32 + lg * 8) = o.v;
+    }
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      s[e] = row_sum16(s[e]);
+      q[e] = row_sum16(q[e]);
+    }
+    if (l15 == 0) {
+      float* rs = &red[0][wave][lg * 8];
+      float* rq = &red[1][wave][lg * 8];
+      *reinterpret_cast<float4*>(rs) = make_float4(s[0], s[1], s[2], s[3]);
+      *reinterpret_cast<float4*>(rs + 4) = make_float4(s[4], s[5], s[6], s[7]);
+      *reinterpret_cast<float4*>(rq) = make_float4(q[0], q[1], q[2], q[3]);
+      *reinterpret_cast<float4*>(rq + 4) = make_float4(q[4], q[5], q[6], q[7]);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < 32) {
+      float ts = red[0][0][t], tq = red[1][0][t];
+      #pragma unroll
+      for (int wv = 1; wv < ST3_WAVES; ++wv) {
+        ts += red[0][wv][t];
+        tq += red[1][wv][t];
+      }
+      psum[blockIdx.x * 32 + t] = ts;
+      psq[blockIdx.x * 32 + t] = tq;
+    }
+    return;
+  }
   float sc[8], bi[8];
   if (scale) {
     load8f(scale + lg * 8, sc);
@@ -599,6 +684,23 @@ __global__ __launch_bounds__(256) void k_stem3_u8(
   }
 }
 
+// output pixels of an N x H x W batch: Ho = (H-1)/2 + 1, Wo likewise
+static long st3_rows(int N, int H, int W) {
+  return (long)N * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+}
+
+static St3Geom st3_geom(long M, int H, int W) {
+  St3Geom g;
+  g.M = (int)M;
+  g.H = H;
+  g.W = W;
+  g.Ho = (H - 1) / 2 + 1;
+  g.Wo = (W - 1) / 2 + 1;
+  make_magic((unsigned)g.Wo, &g.magic_wo, &g.shift_wo);
+  make_magic((unsigned)g.Ho, &g.magic_ho, &g.shift_ho);
+  return g;
+}
+
 // x uint8 [N][H][W][3]; wp bf16 [32][32] (w[k][r][s][c] at 9r + 3s + c, zeros
 // at 27..31); y bf16 [N][Ho][Wo][32] with Ho = (H-1)/2 + 1, Wo likewise;
 // scale/bias fp32 [32] (both or neither); act 0 none / 1 ReLU / 2 ReLU6.
@@ -614,19 +716,229 @@ DDLW_EXPORT int ddlw_stem3_u8_fwd_ep(const void* x, const void* wp, void* y,
     return fail("scale and bias come together");
   if ((((size_t)wp | (size_t)y | (size_t)scale | (size_t)bias) & 15) != 0)
     return fail("wp, y, scale and bias must be 16-byte aligned");
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  const long M = (long)N * Ho * Wo;
+  const long M = st3_rows(N, H, W);
   if (M >= (1l << 31) || (long)N * H * W * 3 >= (1l << 31))
     return fail("N*Ho*Wo and N*H*W*3 must be below 2^31");
   if (M == 0) return 0;
-  unsigned long long mg_wo, mg_ho;
-  unsigned sh_wo, sh_ho;
-  make_magic((unsigned)Wo, &mg_wo, &sh_wo);
-  make_magic((unsigned)Ho, &mg_ho, &sh_ho);
-  hipLaunchKernelGGL(k_stem3_u8, dim3((unsigned)cdiv(M, ST3_BM)), dim3(256), 0,
+  hipLaunchKernelGGL(k_stem3_u8<false>, dim3((unsigned)cdiv(M, ST3_BM)),
+                     dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)x, (const bf16_t*)wp, (bf16_t*)y,
+                     (const float*)scale, (const float*)bias, act,
+                     (float*)nullptr, (float*)nullptr, st3_geom(M, H, W));
+  DDLW_CHECK_LAUNCH();
+}
+
+// Partial rows ddlw_stem3_u8_fwd_stats writes per channel: one per 128-pixel
+// block. Launches nothing; `stream` is there because every export outside the
+// ABI test's pinned query list ends in one.
+DDLW_EXPORT int ddlw_stem3_u8_nparts(long M, void* stream) {
+  (void)stream;
+  return (M < 0 || M >= (1l << 31)) ? -1 : (int)cdiv(M, ST3_BM);
+}
+
+// Training forward: y = conv3x3_s2_p1(normalize(x)) raw, bf16 [N][Ho][Wo][32],
+// and the BN statistics partials of y, psum/psq fp32 [nparts][32] with
+// nparts = ddlw_stem3_u8_nparts(N*Ho*Wo).
+DDLW_EXPORT int ddlw_stem3_u8_fwd_stats(const void* x, const void* wp, void* y,
+                                        void* psum, void* psq, int nparts,
+                                        int N, int H, int W, int C, int K,
+                                        void* stream) {
+  auto fail = [](const char* why) { return ddlw_fail("stem3_u8_fwd_stats", why); };
+  if (C != 3 || K != 32) return fail("takes the 3x3 stride-2 stem with C=3, K=32");
+  if (N < 0 || H < 1 || W < 1) return fail("needs N >= 0 and H, W >= 1");
+  if ((((size_t)wp | (size_t)y) & 15) != 0)
+    return fail("wp and y must be 16-byte aligned");
+  if (psum == nullptr || psq == nullptr || (((size_t)psum | (size_t)psq) & 3) != 0)
+    return fail("psum and psq must be fp32 buffers");
+  const long M = st3_rows(N, H, W);
+  if (M >= (1l << 31) || (long)N * H * W * 3 >= (1l << 31))
+    return fail("N*Ho*Wo and N*H*W*3 must be below 2^31");
+  if (nparts != ddlw_stem3_u8_nparts(M, nullptr))
+    return fail("nparts must be ddlw_stem3_u8_nparts(N*Ho*Wo)");
+  if (M == 0) return 0;
+  hipLaunchKernelGGL(k_stem3_u8<true>, dim3((unsigned)nparts), dim3(256), 0,
                      (hipStream_t)stream, (const unsigned char*)x,
-                     (const bf16_t*)wp, (bf16_t*)y, (const float*)scale,
-                     (const float*)bias, act, (int)M, H, W, Ho, Wo, mg_wo,
-                     sh_wo, mg_ho, sh_ho);
+                     (const bf16_t*)wp, (bf16_t*)y, (const float*)nullptr,
+                     (const float*)nullptr, 0, (float*)psum, (float*)psq,
+                     st3_geom(M, H, W));
+  DDLW_CHECK_LAUNCH();
+}
+
+
+// ---------------------------------------------------------------------------
+// Stem weight gradient from the uint8 batch (no stem dgrad: it is the first
+// layer):  dW[k][r][s][c] = sum_m dy[m][k] * xn[m][9r + 3s + c],  xn gathered
+// by the helper above, so the normalized batch is never read or written.
+// The layer is bound by reading dy (51 MB at batch 64 / 224; the byte gathers
+// hit cache), and the 32 x 27 result is tiny, so this is a VALU kernel with
+// the result in registers and nothing staged through LDS in its loop:
+//   - a lane owns ONE pixel per step, a wave 64 consecutive pixels, and the 4
+//     waves of a block take the same pixels with 8 output channels each:
+//     wave w loads dy[m][8w .. 8w+7] as one 16-byte vector and the pixel's 27
+//     taps as bytes, and keeps 8 x 27 fp32 accumulators. Products of two bf16
+//     values are exact in fp32; only the sum rounds.
+//   - block b walks the 64-pixel groups b, b + nparts, ... in that order; the
+//     next group's loads are issued before the current group's 216 FMAs.
+//   - a pixel past M has its dy vector zeroed and, like a tap outside the
+//     image, every tap zeroed (st3_value), so it adds exactly 0; the pad
+//     slots kk >= 27 are never computed.
+//   - no atomics: a DPP row sum folds 16 lanes, the 4 rows of a wave meet in
+//     LDS and are added in row order, and the block writes ONE partial
+//     part[b][32][27]. k_stem3_u8_wgrad_sum adds the partials in a fixed
+//     order and scatters kk = 9r + 3s + c into the [K][C][R][S] weight layout.
+// ---------------------------------------------------------------------------
+#define ST3W_PIX 64                // pixels per step: one per lane
+#define ST3W_STEPS 4               // a block takes at least this many steps ...
+#define ST3W_MAX_PARTS 256         // ... and there are at most this many blocks
+#define ST3W_SLICES 8              // k_stem3_u8_wgrad_sum: partial slices
+
+struct St3wLoad {
+  uint4 dy;
+  int have;
+  unsigned char b[27];
+};
+
+__global__ __launch_bounds__(256) void k_stem3_u8_wgrad(
+    const unsigned char* __restrict__ x,   // [N][H][W][3]
+    const bf16_t* __restrict__ dy,         // [M][32]
+    float* __restrict__ part,              // [gridDim.x][32][27]
+    St3Geom geo) {
+  __shared__ float red[ST3_WAVES][4][8 * 27];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int ngroups = (geo.M + ST3W_PIX - 1) / ST3W_PIX;   // M < 2^31 - 64
+
+  int off[4][8], need[4][8];
+  #pragma unroll
+  for (int g = 0; g < 4; ++g) st3_taps(g, geo.W, off[g], need[g]);
+
+  auto load = [&](int group) {
+    St3wLoad l;
+    const int m = group * ST3W_PIX + lane;
+    const unsigned char* ctr;
+    l.have = st3_pixel(x, geo, m, ctr);
+    // a pixel past M reads pixel M-1's vector; compute() drops it
+    l.dy = *reinterpret_cast<const uint4*>(
+        dy + (long)(m < geo.M ? m : geo.M - 1) * 32 + wave * 8);
+    #pragma unroll
+    for (int kk = 0; kk < 27; ++kk)
+      l.b[kk] = st3_byte(ctr, off[kk >> 3][kk & 7], need[kk >> 3][kk & 7], l.have);
+    return l;
+  };
+
+  float acc[8][27];
+  #pragma unroll
+  for (int k = 0; k < 8; ++k)
+    #pragma unroll
+    for (int kk = 0; kk < 27; ++kk) acc[k][kk] = 0.f;
+
+  auto compute = [&](const St3wLoad& l) {
+    bf16x8 d;
+    d.v = l.dy;
+    if (!(l.have & ST3_PIXEL)) d.v = make_uint4(0u, 0u, 0u, 0u);
+    float xn[27];
+    #pragma unroll
+    for (int kk = 0; kk < 27; ++kk)
+      xn[kk] = b2f(st3_value(l.b[kk], need[kk >> 3][kk & 7], l.have));
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float dk = b2f(d.h[k]);
+      #pragma unroll
+      for (int kk = 0; kk < 27; ++kk) acc[k][kk] = fmaf(dk, xn[kk], acc[k][kk]);
+    }
+  };
+
+  int group = blockIdx.x;                  // gridDim.x <= ngroups
+  St3wLoad cur = load(group);
+  for (group += gridDim.x; group < ngroups; group += gridDim.x) {
+    const St3wLoad nxt = load(group);
+    compute(cur);
+    cur = nxt;
+  }
+  compute(cur);
+
+  const int l15 = lane & 15;
+  const int lg = lane >> 4;
+  #pragma unroll
+  for (int k = 0; k < 8; ++k)
+    #pragma unroll
+    for (int kk = 0; kk < 27; ++kk) {
+      const float v = row_sum16(acc[k][kk]);
+      if (l15 == 0) red[wave][lg][k * 27 + kk] = v;
+    }
+  __syncthreads();
+  // thread t: entries t, t + 256, ... of the block's [32][27]; channel k of
+  // it came from wave k / 8
+  for (int i = threadIdx.x; i < 32 * 27; i += 256) {
+    const int wv = i / (8 * 27), j = i - wv * (8 * 27);
+    float v = red[wv][0][j];
+    #pragma unroll
+    for (int r = 1; r < 4; ++r) v += red[wv][r][j];
+    part[(long)blockIdx.x * (32 * 27) + i] = v;
+  }
+}
+
+// dw[k][c][r][s] = sum_p part[p][k][9r + 3s + c]: block b takes 32 entries,
+// slice j of 8 adds partials j, j + 8, ... in order, the slices meet in LDS
+// and are added in slice order.
+__global__ __launch_bounds__(256) void k_stem3_u8_wgrad_sum(
+    const float* __restrict__ part, float* __restrict__ dw, int nparts) {
+  __shared__ float red[ST3W_SLICES][32];
+  const int e = threadIdx.x & 31;
+  const int slice = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + e;       // k * 27 + kk; 27 blocks cover 864
+  float v = 0.f;
+  for (int p = slice; p < nparts; p += ST3W_SLICES) v += part[(long)p * (32 * 27) + i];
+  red[slice][e] = v;
+  __syncthreads();
+  if (slice == 0) {
+    #pragma unroll
+    for (int j = 1; j < ST3W_SLICES; ++j) v += red[j][e];
+    const int k = i / 27, kk = i - k * 27;
+    const int r = kk / 9, s = (kk - 9 * r) / 3, c = kk - 9 * r - 3 * s;
+    dw[((k * 3 + c) * 3 + r) * 3 + s] = v;
+  }
+}
+
+// Partials ddlw_stem3_u8_wgrad writes: one per block, a block for every
+// ST3W_STEPS groups of 64 pixels, ST3W_MAX_PARTS (one per CU) at the most.
+DDLW_EXPORT int ddlw_stem3_u8_wgrad_nparts(long M, void* stream) {
+  (void)stream;
+  if (M < 0 || M >= (1l << 31)) return -1;
+  const long n = cdiv(M, ST3W_PIX * ST3W_STEPS);
+  return (int)(n < 1 ? 1 : (n > ST3W_MAX_PARTS ? ST3W_MAX_PARTS : n));
+}
+
+// x uint8 [N][H][W][3]; dy bf16 [N][Ho][Wo][32]; part fp32 scratch
+// [nparts][32][27] with nparts = ddlw_stem3_u8_wgrad_nparts(N*Ho*Wo);
+// dw fp32 [32][3][3][3] (K, C, R, S), every element written.
+DDLW_EXPORT int ddlw_stem3_u8_wgrad(const void* x, const void* dy, void* part,
+                                    void* dw, int nparts, int N, int H, int W,
+                                    int C, int K, void* stream) {
+  auto fail = [](const char* why) { return ddlw_fail("stem3_u8_wgrad", why); };
+  if (C != 3 || K != 32) return fail("takes the 3x3 stride-2 stem with C=3, K=32");
+  if (N < 0 || H < 1 || W < 1) return fail("needs N >= 0 and H, W >= 1");
+  if (((size_t)dy & 15) != 0) return fail("dy must be 16-byte aligned");
+  if (part == nullptr || dw == nullptr || (((size_t)part | (size_t)dw) & 3) != 0)
+    return fail("part and dw must be fp32 buffers");
+  const long M = st3_rows(N, H, W);
+  if (M >= (1l << 31) - ST3W_PIX || (long)N * H * W * 3 >= (1l << 31))
+    return fail("N*Ho*Wo and N*H*W*3 must be below 2^31");
+  if (nparts != ddlw_stem3_u8_wgrad_nparts(M, nullptr))
+    return fail("nparts must be ddlw_stem3_u8_wgrad_nparts(N*Ho*Wo)");
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) {
+    if (hipMemsetAsync(dw, 0, 32 * 27 * sizeof(float), st) != hipSuccess) {
+      ddlw_set_error("stem3_u8_wgrad: clearing dw failed");
+      return 1;
+    }
+    return 0;
+  }
+  hipLaunchKernelGGL(k_stem3_u8_wgrad, dim3((unsigned)nparts), dim3(256), 0, st,
+                     (const unsigned char*)x, (const bf16_t*)dy, (float*)part,
+                     st3_geom(M, H, W));
+  DDLW_CHECK_LAUNCH_OR_RETURN();
+  hipLaunchKernelGGL(k_stem3_u8_wgrad_sum, dim3(27), dim3(256), 0, st,
+                     (const float*)part, (float*)dw, nparts);
   DDLW_CHECK_LAUNCH();
 }

@@ -290,10 +290,7 @@ DDLW_EXPORT int ddlw_conv_wgrad(const void* dy, const void* x, const void* zpage
   else WLAUNCH(64, 64);
 #undef WLAUNCH
 #undef WLAUNCH3
-  {
-    hipError_t err_ = hipGetLastError();
-    if (err_ != hipSuccess) { ddlw_set_error(hipGetErrorString(err_)); return 1; }
-  }
+  DDLW_CHECK_LAUNCH_OR_RETURN();
   long elems = (long)K * R * S * C;
   long g = cdiv(elems, 32);
   if (g > 4096) g = 4096;
@@ -574,10 +571,7 @@ DDLW_EXPORT int ddlw_conv_wgrad3x3(const void* dy, const void* x,
                        (const bf16_t*)zpage, (float*)slab, N, H, W_, C, K,
                        (int)(rows / split), (int)(rows % split), mg_h, sh_h);
   });
-  {
-    hipError_t err_ = hipGetLastError();
-    if (err_ != hipSuccess) { ddlw_set_error(hipGetErrorString(err_)); return 1; }
-  }
+  DDLW_CHECK_LAUNCH_OR_RETURN();
   long elems = (long)K * 9 * C;
   long g = cdiv(elems, 32);
   if (g > 4096) g = 4096;

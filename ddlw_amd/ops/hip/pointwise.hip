@@ -157,21 +157,6 @@ __global__ __launch_bounds__(256) void k_pw_conv(
   }
 }
 
-// Sum over the 16 lanes of a DPP row (= the 16 rows l15 of one channel
-// group): rotate by 8, 4, 2, 1 within the row. Every lane ends with the total.
-template <int CTRL>
-__device__ __forceinline__ float pw_row_ror_add(float v) {
-  const int i = __float_as_int(v);
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float pw_row_sum16(float v) {
-  v = pw_row_ror_add<0x128>(v);  // row_ror:8
-  v = pw_row_ror_add<0x124>(v);  // row_ror:4
-  v = pw_row_ror_add<0x122>(v);  // row_ror:2
-  return pw_row_ror_add<0x121>(v);  // row_ror:1
-}
-
 // k_pw_conv_stats — the training forward: y = x * w^T with no epilogue math,
 // plus the BatchNorm statistics of y as per-block partial rows
 //   psum[mtile][k] = sum over the block's 128 rows of y[m][k],  psq: of y^2
@@ -222,8 +207,8 @@ __global__ __launch_bounds__(256) void k_pw_conv_stats(
     }
     #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      s[e] = pw_row_sum16(s[e]);
-      q[e] = pw_row_sum16(q[e]);
+      s[e] = row_sum16(s[e]);
+      q[e] = row_sum16(q[e]);
     }
     if (l15 == 0) {
       float* rs = &red[0][wave][p * 32 + lg * 8];

@@ -10,6 +10,8 @@ batch, the frozen stem (normalize, 3->32 conv, BN, ReLU6) is one kernel too.
 A training-mode block (the fine-tuned suffix) runs its two pointwise stages on
 ``_PwConvBnActFn``: the conv kernel emits the BN statistics from its epilogue
 and the backward runs on the pointwise dgrad and the split-K wgrad kernels.
+A marked training stem fed a uint8 batch runs on ``_StemU8BnActFn`` the same
+way, its forward and its weight gradient reading the bytes.
 """
 from __future__ import annotations
 
@@ -140,10 +142,22 @@ def stem_u8_fusable(net, x) -> bool:
     return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
 
 
-def _stem3_packed(conv) -> torch.Tensor:
+def _stem_trains(conv, bn) -> bool:
+    """A stem with a parameter that wants a gradient: its weight, BN affine
+    and running statistics move under the kernels (fused optimizers,
+    ``bn_finalize``), which write through raw pointers and bump no
+    ``_version``, so nothing derived from them may be cached."""
+    return (conv.weight.requires_grad or bn.weight.requires_grad
+            or bn.bias.requires_grad)
+
+
+def _stem3_packed(conv, fresh: bool = False) -> torch.Tensor:
     """``binding.stem3_pack_weight(conv.weight)``, cached on the module until
-    the weight mutates or moves (as ``folded_scale_bias`` caches)."""
+    the weight mutates or moves (as ``folded_scale_bias`` caches);
+    ``fresh=True`` packs the live weight and leaves the cache alone."""
     w = conv.weight
+    if fresh:
+        return binding.stem3_pack_weight(w)
     key = (w._version, w.data_ptr(), w.device)
     cached = getattr(conv, "_stem3_cache", None)
     if cached is not None and cached[0] == key:
@@ -154,13 +168,121 @@ def _stem3_packed(conv) -> torch.Tensor:
 
 
 @torch.no_grad()
-def stem_u8_forward(net, x: torch.Tensor) -> torch.Tensor:
-    """``features[0:3]`` of a frozen MobileNetV2 on a uint8 batch: one
-    launch (``stem_u8_fusable`` is the caller's to check)."""
+def stem_u8_forward(net, x: torch.Tensor, fresh: bool = False) -> torch.Tensor:
+    """``features[0:3]`` of a MobileNetV2 in eval mode on a uint8 batch: one
+    launch (``stem_u8_fusable`` is the caller's to check). A frozen stem
+    uses the cached weight pack and BN fold. ``fresh=True`` is for a
+    trainable stem that is being evaluated between training steps
+    (validation during ``fit``): its weight, BN affine and running statistics
+    move under kernels that bump no ``_version``, so the pack and the fold
+    are computed from the live tensors on every call."""
     conv, bn = net.features[0], net.features[1]
-    scale, bias = bn.folded_scale_bias()
+    scale, bias = bn.folded_scale_bias(fresh=fresh)
     return binding.stem3_u8_fwd_ep(x, conv.weight, scale, bias, _ACT[bn.act],
-                                   wp=_stem3_packed(conv))
+                                   wp=_stem3_packed(conv, fresh=fresh))
+
+
+# Measured loser by the project's rule (docs/KERNELS.md, "MobileNetV2 stem from
+# uint8, training"): at batch 64 / 224 the stage ran 1.03-1.10x the module
+# path's speed on medians in three runs, by more than that path's spread in
+# only one of them, and the from-scratch step stayed inside its spread. So
+# the route is opt-in twice: the mark, and this switch.
+_STEM_U8_TRAIN_DEFAULT = "0"
+
+
+def stem_u8_train_enabled() -> bool:
+    """The A/B switch of the training-mode uint8 stem, read at call time:
+    ``DDLW_STEM_U8_TRAIN=1`` puts a marked training stem on the stage
+    Function, ``0`` (the default, see above) leaves it on normalize + module
+    conv + BatchNormAct2d."""
+    return os.environ.get("DDLW_STEM_U8_TRAIN", _STEM_U8_TRAIN_DEFAULT) != "0"
+
+
+def stem_u8_train_fusable(net, x) -> bool:
+    """The conditions under which a TRAINING stem (``net.features[0:3]``)
+    takes a uint8 batch on ``_StemU8BnActFn``: the opt-in mark on the stem
+    conv (``Conv2d.u8_train``, set by ``MobileNetV2.enable_u8_train_stem``,
+    which ``apply_bf16_policy`` calls), grad enabled, the stem BN in training
+    mode, a gradient wanted by the conv weight or the BN affine, a CUDA uint8
+    channels_last 4-D batch, the 3->32 3x3 stride-2 pad-1 bias-free conv with
+    bf16 weights, fp32 BN statistics, neither of ``DDLW_DISABLE_HIP_OPS=1``
+    and ``DDLW_CONV=stock``, and ``DDLW_STEM_U8_TRAIN=1`` (default ``0``,
+    ``stem_u8_train_enabled``). All read at call time."""
+    conv, bn = net.features[0], net.features[1]
+    if not getattr(conv, "u8_train", False):
+        return False
+    if not (torch.is_grad_enabled() and bn.training):
+        return False
+    if not _stem_trains(conv, bn):
+        return False
+    if not (x.is_cuda and x.dtype == torch.uint8):
+        return False
+    if os.environ.get("DDLW_DISABLE_HIP_OPS", "0") == "1":
+        return False
+    if os.environ.get("DDLW_CONV", "auto") == "stock":
+        return False
+    if not stem_u8_train_enabled():
+        return False
+    if not (_is_stem3(conv) and _bn_fp32(bn)):
+        return False
+    return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+
+
+class _StemU8BnActFn(torch.autograd.Function):
+    """normalize -> conv3x3/s2 -> BatchNormAct2d of a training-mode stem fed
+    a uint8 batch; mirrors ``_PwConvBnActFn``. Forward: the stem kernel reads
+    the bytes and writes the conv output and its BN statistics partials in
+    one pass (no normalized batch, no ``k_bn_stats`` re-read), ``bn_finalize``
+    turns them into mean / rstd and updates the running buffers, ``bn_apply``
+    normalizes. Backward: BN reduce, BN dx, then the weight gradient from the
+    bytes again. No dx: the stem is the first layer."""
+
+    @staticmethod
+    def forward(ctx, x_u8, weight, wp, gamma, beta, running_mean, running_var,
+                momentum: float, eps: float, act: int):
+        k = weight.shape[0]
+        y, ps, pq, nparts = binding.stem3_u8_fwd_stats(x_u8, weight, wp=wp)
+        rows = y.shape[0] * y.shape[2] * y.shape[3]
+        mean, rstd = binding.bn_finalize_parts(
+            ps, pq, nparts, rows, k, eps, momentum, running_mean, running_var)
+        out, mask = binding.bn_apply(y, None, mean, rstd, gamma, beta, act)
+        if mask is None:
+            mask = x_u8.new_empty(0, dtype=torch.uint8)
+        ctx.save_for_backward(x_u8, y, mask, mean, rstd, gamma)
+        ctx.relu = bool(act)  # the mask bit means "gradient passes"
+        ctx.weight_shape = tuple(weight.shape)
+        ctx.weight_dtype = weight.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x_u8, y, mask, mean, rstd, gamma = ctx.saved_tensors
+        dout = dout.contiguous(memory_format=torch.channels_last)
+        if dout.dtype != torch.bfloat16:
+            dout = dout.to(torch.bfloat16)
+        dbeta, dgamma = binding.bn_bwd_reduce(dout, mask, y, mean, rstd, ctx.relu)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dy, _ = binding.bn_bwd_dx(dout, mask, y, mean, rstd, gamma, dbeta,
+                                      dgamma, ctx.relu, False)
+            dw = binding.stem3_u8_wgrad(x_u8, dy, ctx.weight_shape).to(ctx.weight_dtype)
+        return None, dw, None, dgamma, dbeta, None, None, None, None, None
+
+
+def stem_u8_train_forward(net, x: torch.Tensor) -> torch.Tensor:
+    """``features[0:3]`` of a training MobileNetV2 on a uint8 batch, on the
+    stage Function (``stem_u8_train_fusable`` is the caller's to check); the
+    BN module's bookkeeping is done here as its forward does. The weight is
+    packed anew on every call (864 values): the optimizer kernels update it
+    without a ``_version`` bump, so a cached pack would be the first step's."""
+    conv, bn = net.features[0], net.features[1]
+    bn.num_batches_tracked += 1
+    w, b = bn.weight, bn.bias
+    if w.dtype != torch.float32:
+        w, b = w.float(), b.float()
+    return _StemU8BnActFn.apply(x, conv.weight, _stem3_packed(conv, fresh=True), w, b,
+                                bn.running_mean, bn.running_var, bn.momentum,
+                                bn.eps, _ACT[bn.act])
 
 
 def normalize_u8_input(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:

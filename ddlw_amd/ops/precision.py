@@ -20,11 +20,18 @@ def apply_bf16_policy(module: nn.Module) -> nn.Module:
     fused BN kernels read them as fp32). A pure cast: ``Parameter`` objects
     and their ``requires_grad`` flags are kept (a ``fine_tune_at`` split
     survives), a second call changes nothing, and it works on a CPU module.
-    Build optimizers AFTER it, so fp32 masters start from the cast weights."""
+    Build optimizers AFTER it, so fp32 masters start from the cast weights.
+
+    The policy is also the door to the opt-in kernel routes: a submodule with
+    ``enable_u8_train_stem`` (MobileNetV2) gets its training stem marked for
+    the uint8 stem kernels. The mark is an instance attribute, so it is not
+    saved: a reloaded model is unmarked until the policy is applied again."""
     module = module.to(memory_format=torch.channels_last)
     for mod in module.modules():
         if isinstance(mod, (nn.Conv2d, nn.Linear)):
             mod.to(torch.bfloat16)
+        if hasattr(mod, "enable_u8_train_stem"):
+            mod.enable_u8_train_stem()
     return module
 
 
