@@ -41,6 +41,15 @@ step (``fine_tune_at=0``) from a uint8 batch, ``DDLW_STEM_U8_TRAIN=1`` vs
 ``=0``. Same alternation, same rule (``mbconv.stem_u8_train_enabled`` holds
 the verdict); ``--only-stem-u8-train`` runs just these two.
 
+The depthwise training stage (``dw_fwd+stats`` / ``dw_bwd`` rows,
+``dw_train_step_at_13``, ``dw_train_scratch_step_u8``): every distinct
+depthwise shape, ``depthwise_fwd_stats`` + finalize vs ``depthwise_fwd`` +
+``bn_stats`` and, at stride 1, ``depthwise_bwd_bn`` vs ``bn_bwd_dx`` + dgrad +
+wgrad; then the ``fine_tune_at=13`` step and the from-scratch uint8 step,
+``DDLW_DW_TRAIN=1`` vs ``=0``. Same alternation, same rule
+(``binding.dw_train_route`` holds the per-shape verdicts);
+``--only-dw-train`` runs just these.
+
 The facade (``facade_head_step_u8``): the head-training step from a uint8
 batch through ``train.Model(precision="bf16")`` with the metrics read back
 every step (``train_step``) and kept on the device (the ``fit``-path step),
@@ -283,6 +292,97 @@ def bench_pointwise_train(B, H, C, K, dev, iters, rounds):
                          **rec,
                          "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)})
     return recs
+
+
+def bench_depthwise_train(B, H, C, stride, dev, iters, rounds):
+    """The depthwise training stage of one shape, ours ("fused") against the
+    kernels it replaces ("unfused"): forward ``depthwise_fwd_stats`` +
+    finalize vs ``depthwise_fwd`` + ``bn_stats``; at stride 1 the backward
+    after the reduce, ``depthwise_bwd_bn`` vs ``bn_bwd_dx`` + dgrad + wgrad."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    w = torch.randn(C, 1, 3, 3, device=dev).to(torch.bfloat16)
+    rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+    gamma = torch.empty(C, device=dev).uniform_(0.5, 1.5)
+    beta = torch.empty(C, device=dev).uniform_(2.0, 4.0)
+    eps, mom = 1e-5, 0.1
+    y = binding.depthwise_fwd(x, w, stride, 1)
+    Ho = y.shape[2]
+    M = B * Ho * Ho
+    dout = _cl(torch.randn(B, C, Ho, Ho, device=dev).to(torch.bfloat16))
+    mean, rstd = binding.bn_stats(y, eps, mom, None, None)
+    _, mask = binding.bn_apply(y, None, mean, rstd, gamma, beta, 2)
+    dbeta, dgamma = binding.bn_bwd_reduce(dout, mask, y, mean, rstd, True)
+
+    def fwd_ours():
+        yy, ps, pq, nparts = binding.depthwise_fwd_stats(x, w, stride, 1)
+        return yy, binding.bn_finalize_parts(ps, pq, nparts, M, C, eps, mom, rm, rv)
+
+    def fwd_parts():
+        yy = binding.depthwise_fwd(x, w, stride, 1)
+        return yy, binding.bn_stats(yy, eps, mom, rm, rv)
+
+    def bwd_ours():
+        return binding.depthwise_bwd_bn(dout, mask, y, x, w, mean, rstd, gamma,
+                                        dbeta, dgamma, True, True)
+
+    def bwd_parts():
+        dz, _ = binding.bn_bwd_dx(dout, mask, y, mean, rstd, gamma, dbeta,
+                                  dgamma, True, False)
+        return (binding.depthwise_dgrad(dz, w, x.shape, stride, 1),
+                binding.depthwise_wgrad(dz, x, w.shape, stride, 1))
+
+    # the bytes the fused kernels must move: x read, y written (+ dout, y, x
+    # read and dx written by the backward)
+    T_in, T = 2.0 * B * H * H * C, 2.0 * M * C
+    contenders = {"fwd+stats": (fwd_ours, fwd_parts, T_in + T)}
+    if stride == 1:
+        contenders["bwd"] = (bwd_ours, bwd_parts, 2 * T + 2 * T_in)
+    recs = []
+    with torch.no_grad():
+        for direction, (ours, parts, bytes_io) in contenders.items():
+            a, b = ours()[0], parts()[0]
+            err = ((a.float() - b.float()).abs().max()
+                   / (b.float().abs().max() + 1e-6)).item()
+            s = time_interleaved({"fused": ours, "unfused": parts}, iters, rounds)
+            rec = _verdict(s)
+            recs.append({"kind": "dw_" + direction, "shape": f"n{B}_h{H}_c{C}_s{stride}",
+                         "M": M, "C": C, "rel_err_vs_unfused": round(err, 5), **rec,
+                         "spread_fused": round(max(s["fused"]) - min(s["fused"]), 4),
+                         "gbps_fused": round(bytes_io / rec["ms_fused"] / 1e6, 1)})
+    return recs
+
+
+def bench_dw_train_step(B, k, dev, iters, rounds, u8=False):
+    """One training step with ``features[k:]`` trainable (``k = 0`` on a uint8
+    batch is the from-scratch step): ``DDLW_DW_TRAIN=1`` ("fused") vs ``=0``
+    ("unfused"), alternating in one process."""
+    torch.manual_seed(0)
+    if u8:
+        x = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8,
+                          device=dev).permute(0, 3, 1, 2)
+    else:
+        x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
+    labels = torch.randint(0, 5, (B,), device=dev)
+    model = apply_bf16_policy(build_model(224, 224, 3, 5, fine_tune_at=k).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    s = time_interleaved({"fused": _with_env("DDLW_DW_TRAIN", "1", step),
+                          "unfused": _with_env("DDLW_DW_TRAIN", "0", step)},
+                         iters, rounds)
+    rec = _verdict(s)
+    rec["spread_fused"] = round(max(s["fused"]) - min(s["fused"]), 4)
+    for name in ("fused", "unfused"):
+        rec[f"img_s_{name}"] = round(B / rec[f"ms_{name}"] * 1e3, 1)
+    rec["not_slower"] = bool(rec["ms_fused"] - rec["ms_unfused"] <= rec["spread_unfused"])
+    return rec
 
 
 def _with_env(name, value, fn):
@@ -613,6 +713,8 @@ def main():
                     help="skip the Model-facade and Adadelta-step sections")
     ap.add_argument("--only-stem-u8-train", action="store_true",
                     help="run only the training-stem-from-uint8 stage and step")
+    ap.add_argument("--only-dw-train", action="store_true",
+                    help="run only the depthwise training stage rows and steps")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -620,7 +722,7 @@ def main():
         sys.exit("bench_mobilenet: no GPU (timings are only meaningful on the device)")
     dev = torch.device("cuda:0")
     B = args.batch
-    if args.only_stem_u8_train:
+    if args.only_stem_u8_train or args.only_dw_train:
         args.skip_layers = args.skip_e2e = args.skip_facade = True
     layers = []
     train_layers = []
@@ -642,6 +744,13 @@ def main():
                 train_layers.append(rec)
                 print(json.dumps(rec), flush=True)
         _table(train_layers)
+    dw_train = []
+    if args.only_dw_train or (not args.skip_layers and not args.skip_train):
+        for (H, C, st) in layer_shapes(224)[1]:
+            for rec in bench_depthwise_train(B, H, C, st, dev, args.iters, args.rounds):
+                dw_train.append(rec)
+                print(json.dumps(rec), flush=True)
+        _table(dw_train)
     if not args.skip_layers and not args.skip_frozen:
         pw, dw = layer_shapes(224)
         for (H, C, K, act, res) in pw:
@@ -669,6 +778,12 @@ def main():
         r = bench_scratch_step_u8(B, dev, args.e2e_iters, args.rounds)
         finetune["scratch_step_u8"] = r
         print(json.dumps({"scratch_step_u8": r}), flush=True)
+    if args.only_dw_train or (not args.skip_e2e and not args.skip_train):
+        for name, k, u8 in (("dw_train_step_at_13", 13, False),
+                            ("dw_train_scratch_step_u8", 0, True)):
+            r = bench_dw_train_step(B, k, dev, args.e2e_iters, args.rounds, u8=u8)
+            finetune[name] = r
+            print(json.dumps({name: r}), flush=True)
     e2e = ({} if args.skip_e2e or args.skip_frozen
            else bench_end_to_end(B, dev, args.e2e_iters, args.rounds))
     if e2e:
@@ -687,7 +802,8 @@ def main():
               f"unfused {r['ms_unfused']:.3f} ms ({r['img_s_unfused']} img/s)  "
               f"spread {r['spread_unfused']:.3f}  speedup {r['speedup']}")
     report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers,
-              "train_layers": train_layers, "stem_u8": stem,
+              "train_layers": train_layers, "dw_train_layers": dw_train,
+              "stem_u8": stem,
               "stem_u8_train": stem_train, **finetune, **e2e, **facade}
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)

@@ -71,6 +71,10 @@ SIGNATURES = {
     # depthwise.hip
     "ddlw_depthwise_fwd": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_depthwise_fwd_ep": (_I, [_P] * 5 + [_I] * 9 + [_P]),
+    "ddlw_depthwise_fwd_stats_nparts": (_I, [_L, _I, _P]),
+    "ddlw_depthwise_fwd_stats": (_I, [_P] * 5 + [_I] * 8 + [_P]),
+    "ddlw_depthwise_bwd_bn_nparts": (_I, [_I, _I, _I, _P]),
+    "ddlw_depthwise_bwd_bn": (_I, [_P] * 13 + [_I] * 5 + [_P]),
     "ddlw_depthwise_dgrad": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_depthwise_wgrad_nparts": (_I, [_L, _I]),
     "ddlw_depthwise_wgrad": (_I, [_P, _P, _P, _P] + [_I] * 10 + [_P]),

@@ -648,6 +648,94 @@ def depthwise_wgrad(dy: torch.Tensor, x: torch.Tensor, weight_shape,
     return dw
 
 
+# ---- depthwise conv + BatchNorm, training path ------------------------------ #
+
+
+def dw_train_route(direction: str, C: int, stride: int, M: int) -> bool:
+    """True: this direction (``"fwd"`` = forward + BN statistics, ``"bwd"`` =
+    the stride-1 backward after the BN reduce) of a depthwise 3x3 training
+    stage with C channels and M = N*Ho*Wo output rows runs on the fused
+    kernel; False: on the kernels it replaces. Verdicts of the table in
+    docs/KERNELS.md, "Depthwise conv + BN, training path" (MobileNetV2 @224,
+    batch 64, two runs)."""
+    if direction not in ("fwd", "bwd"):
+        raise ValueError(f"dw_train_route: unknown direction {direction!r}")
+    if direction == "bwd":
+        # every measured stride-1 shape won (1.01x-1.77x, outside the spread)
+        return stride == 1  # no fused stride-2 backward
+    # The forward is 1.06x-1.38x on medians at every shape, but from 56x56
+    # stride 2 down (M <= 50176) both contenders are ~0.04 ms of launch
+    # overhead and the replaced pair's spread (0.008-0.012 ms) covers the
+    # difference in at least one run of two: not a win by the rule. Below
+    # the smallest measured row count nothing is measured and the shape
+    # stays on the fused kernel.
+    return not (3136 <= M <= 50176)
+
+
+@functools.lru_cache(maxsize=512)
+def _depthwise_fwd_stats_nparts(rows: int, C: int) -> int:
+    return int(query("depthwise_fwd_stats_nparts", rows, C, None))
+
+
+def depthwise_fwd_stats(x: torch.Tensor, weight: torch.Tensor, stride: int,
+                        padding: int, parts=None):
+    """Training forward of a depthwise 3x3 conv (stride 1 or 2) with the
+    BatchNorm statistics of its output from the epilogue: returns ``(y,
+    part_sum, part_sumsq, nparts)`` with the partials fp32 ``[nparts, C]``,
+    sums over the bf16 ``y``, ``nparts <= 512``, for ``bn_finalize_parts``.
+    ``parts``: a pair of contiguous fp32 ``[nparts, C]`` tensors to write
+    into."""
+    n, c, h, w = x.shape
+    assert tuple(weight.shape) == (c, 1, 3, 3), "depthwise_fwd_stats: weight must be [C,1,3,3]"
+    if c % 8 != 0:
+        raise ValueError(f"depthwise_fwd_stats: C={c} must be a multiple of 8")
+    ho = (h + 2 * padding - 3) // stride + 1
+    wo = (w + 2 * padding - 3) // stride + 1
+    nparts = _depthwise_fwd_stats_nparts(n * ho * wo, c)
+    if parts is None:
+        both = torch.empty(2, nparts, c, dtype=torch.float32, device=x.device)
+        ps, pq = both[0], both[1]
+    else:
+        ps, pq = parts
+        for t in (ps, pq):
+            assert (t.dtype == torch.float32 and t.is_contiguous()
+                    and tuple(t.shape) == (nparts, c)), "depthwise_fwd_stats: parts"
+    y = torch.empty((n, c, ho, wo), dtype=torch.bfloat16, device=x.device,
+                    memory_format=torch.channels_last)
+    launch("depthwise_fwd_stats", _nhwc(x), _depthwise_w_t(weight), _nhwc(y),
+           ps, pq, n, h, w, c, ho, wo, stride, padding)
+    return y, ps, pq, nparts
+
+
+def depthwise_bwd_bn(dout, mask, y, x, weight, mean, rstd, gamma, dbeta,
+                     dgamma, relu: bool, need_dx: bool):
+    """Backward of a stride-1 pad-1 depthwise 3x3 conv + BatchNorm stage after
+    ``bn_bwd_reduce``, in one kernel: ``dz = bn_bwd_dx(dout, mask, y, ...)``
+    is recomputed per tile and feeds the conv's input and weight gradients
+    without being stored. Returns ``(dx | None, dw)``: dx channels_last bf16
+    like ``x`` (``None`` without ``need_dx``), dw fp32 ``[C,1,3,3]``. No
+    atomics, bit-reproducible."""
+    n, c, h, w = x.shape
+    assert tuple(y.shape) == tuple(dout.shape) == (n, c, h, w), \
+        "depthwise_bwd_bn: stride 1, pad 1 (the output has the input's shape)"
+    assert tuple(weight.shape) == (c, 1, 3, 3), "depthwise_bwd_bn: weight must be [C,1,3,3]"
+    if c % 8 != 0:
+        raise ValueError(f"depthwise_bwd_bn: C={c} must be a multiple of 8")
+    if relu:
+        assert mask is not None and mask.dtype == torch.uint8 \
+            and mask.numel() == n * h * w * (c // 8), "depthwise_bwd_bn: mask"
+    nparts = int(query("depthwise_bwd_bn_nparts", n, h, w, None))
+    part = torch.empty(nparts, 9, c, dtype=torch.float32, device=x.device)
+    dw = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
+    dx = (torch.empty((n, c, h, w), dtype=torch.bfloat16, device=x.device,
+                      memory_format=torch.channels_last) if need_dx else None)
+    launch("depthwise_bwd_bn", _nhwc(dout), mask if relu else None, _nhwc(y),
+           _nhwc(x), _depthwise_w_t(weight), _f32c(mean, c), _f32c(rstd, c),
+           _f32c(gamma, c), _f32c(dbeta, c), _f32c(dgamma, c), dx, part, dw,
+           n, h, w, c, 1 if relu else 0)
+    return dx, dw
+
+
 def dropout_fwd(x: torch.Tensor, p: float, seed: int):
     """K7: bitmask dropout (counter-based RNG, deterministic per seed).
     Returns (y, mask); x flat-size must be a multiple of 8."""

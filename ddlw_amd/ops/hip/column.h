@@ -71,3 +71,25 @@ __device__ __forceinline__ void rowgroup_reduce8(const ColumnGeom& cg, float* ld
     for (int k = 0; k < 8; ++k) v[k] = a[k];
   }
 }
+
+// The same reduction with the block barrier passed in, for kernels compiled
+// with other target features than the runtime headers: __syncthreads would
+// stay an out-of-line call inside them, so they pass a barrier that inlines.
+template <class Barrier>
+__device__ __forceinline__ void rowgroup_reduce8(const ColumnGeom& cg, float* lds,
+                                                 float (&v)[8], Barrier barrier) {
+  const int tid = threadIdx.x;
+  #pragma unroll
+  for (int k = 0; k < 8; ++k) lds[tid * 8 + k] = v[k];
+  barrier();
+  if (cg.rowg() == 0) {
+    float a[8];
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = v[k];
+    for (int g = 1; g < cg.ROWG; ++g)
+      #pragma unroll
+      for (int k = 0; k < 8; ++k) a[k] += lds[(g * cg.VPB + cg.lane_vec()) * 8 + k];
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = a[k];
+  }
+}

@@ -1,6 +1,7 @@
 // Depthwise conv2d (K2 — MobileNetV2's depthwise blocks), NHWC bf16, fp32
 // accumulation: training forward, eval forward with the folded-BN epilogue,
-// and the 3x3 backward (dgrad, wgrad + finalize).
+// the 3x3 backward (dgrad, wgrad + finalize), and the training stage fused
+// with its BatchNorm (forward with statistics, stride-1 BN dx + dgrad + wgrad).
 // Data conventions of the whole family: C % 8 == 0, 16-byte bf16x8 accesses,
 // weights pre-transposed host-side to [R*S][C] so the per-tap weight read is
 // the same contiguous vector shape as the activation read.
@@ -279,6 +280,329 @@ __global__ __launch_bounds__(256) void k_depthwise_wgrad_finalize(
   }
 }
 
+// A loop-invariant bf16x8 vector stays packed (4 VGPRs) across a loop: without
+// this the compiler hoists its bf16 -> fp32 unpacking out of the loop and the
+// nine tap weight vectors cost 72 VGPRs instead of 36.
+__device__ __forceinline__ void keep_packed(uint4& v) {
+  asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+}
+
+// The training kernels below are compiled without packed fp32 arithmetic
+// (v_pk_fma_f32 and its kin), so every FMA of theirs is a plain VALU op on
+// single registers: with the packed forms, which want aligned register pairs,
+// the DX instances of k_depthwise_bwd_bn spill at 256 VGPRs.
+// Side effect: a function of the runtime headers that is not always_inline
+// (make_uint4, make_float4, __syncthreads) has other target features than
+// these kernels and would stay an out-of-line CALL inside them, a full
+// s_waitcnt in the tap loops. So they use none: dw_zero, dw_store4 and
+// dw_barrier below inline, and the device assembly of both kernels is
+// call-free (no s_swappc_b64).
+#define DW_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+typedef float dw_f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void dw_zero(bf16x8& v) {
+  v.v.x = 0u; v.v.y = 0u; v.v.z = 0u; v.v.w = 0u;
+}
+
+// The zeroing of an out-of-range tap as four ANDs with an all-ones / zero
+// mask: written as `if (!ok) zero`, it is compiled to a divergent branch per
+// tap, which ends the basic block, and every tap load then gets its own
+// s_waitcnt vmcnt(0) instead of all nine being in flight.
+__device__ __forceinline__ void dw_keep_if(bf16x8& v, bool ok) {
+  const u32 m = ok ? 0xffffffffu : 0u;
+  v.v.x &= m; v.v.y &= m; v.v.z &= m; v.v.w &= m;
+}
+
+__device__ __forceinline__ void dw_store4(float* p, float a, float b, float c, float d) {
+  *reinterpret_cast<dw_f32x4*>(p) = dw_f32x4{a, b, c, d};
+}
+
+// __syncthreads, spelled out
+__device__ __forceinline__ void dw_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// ---------------------------------------------------------------------------
+// Training forward with the BatchNorm statistics of its output, 3x3: the
+// wgrad's column geometry instead of k_depthwise_fwd's grid-stride loop. A
+// thread owns one 8-channel vector column, keeps the nine tap weight vectors
+// in registers for the whole kernel and streams output pixels (neighbouring
+// row groups sit on neighbouring pixels, so the tap re-reads hit cache). The
+// statistics are the sums of the bf16-ROUNDED outputs and their squares (what
+// k_bn_stats would read back), folded across row groups through LDS in fixed
+// order; block (., y) owns partial row y. No atomics.
+// ---------------------------------------------------------------------------
+template <int STRIDE>
+__global__ __launch_bounds__(256) DW_NO_PK_F32 void k_depthwise_fwd_stats(
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ w_t,
+    bf16_t* __restrict__ y, float* __restrict__ psum, float* __restrict__ psq,
+    int N, int H, int W_, int C, int Ho, int Wo, int pad) {
+  const ColumnGeom cg(C);
+  const int ROWG = cg.ROWG;
+  const int vec = cg.vec(), rowg = cg.rowg();
+  const bool active = cg.active();              // idle threads reach the barriers
+
+  float s[8] = {0}, q[8] = {0};
+  if (active) {
+    bf16x8 vw[DW_K * DW_K];
+    #pragma unroll
+    for (int t = 0; t < DW_K * DW_K; ++t)
+      vw[t].v = *reinterpret_cast<const uint4*>(w_t + (long)t * C + (long)vec * 8);
+    // 32-bit pixel indexing, no unrolling across rows (k_depthwise_wgrad_part)
+    const int rows = N * Ho * Wo;
+    const int rstride = (int)gridDim.y * ROWG;
+    #pragma unroll 1
+    for (int p = (int)blockIdx.y * ROWG + rowg; p < rows; p += rstride) {
+      const unsigned wo = (unsigned)p % (unsigned)Wo;
+      const unsigned t = (unsigned)p / (unsigned)Wo;
+      const int ho = (int)(t % (unsigned)Ho);
+      const int n = (int)(t / (unsigned)Ho);
+      const int hb = ho * STRIDE - pad, wb = (int)wo * STRIDE - pad;
+      bf16x8 vx[DW_K * DW_K];
+      #pragma unroll
+      for (int r = 0; r < DW_K; ++r) {
+        const int h = hb + r;
+        const bool okr = (h >= 0) && (h < H);
+        const int hc = clamp_tap(h, H - 1);
+        #pragma unroll
+        for (int c = 0; c < DW_K; ++c) {
+          const int w = wb + c;
+          const bool ok = okr && (w >= 0) && (w < W_);
+          const int wc = clamp_tap(w, W_ - 1);
+          vx[r * DW_K + c].v = *reinterpret_cast<const uint4*>(
+              x + (long)((n * H + hc) * W_ + wc) * C + (long)vec * 8);
+          dw_keep_if(vx[r * DW_K + c], ok);
+        }
+      }
+      float acc[8] = {0};
+      #pragma unroll
+      for (int t9 = 0; t9 < DW_K * DW_K; ++t9) {
+        keep_packed(vw[t9].v);
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += b2f(vx[t9].h[k]) * b2f(vw[t9].h[k]);
+      }
+      bf16x8 o;
+      #pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        o.h[k] = f2b(acc[k]);
+        const float f = b2f(o.h[k]);
+        s[k] += f;
+        q[k] += f * f;
+      }
+      *reinterpret_cast<uint4*>(y + (long)p * C + (long)vec * 8) = o.v;
+    }
+  }
+  __shared__ float lds[256 * 8];
+  if (ROWG > 1) {                               // block-uniform
+    rowgroup_reduce8(cg, lds, s, dw_barrier);
+    dw_barrier();
+    rowgroup_reduce8(cg, lds, q, dw_barrier);
+  }
+  if (active && rowg == 0) {
+    float* os = psum + (long)blockIdx.y * C + (long)vec * 8;
+    float* oq = psq + (long)blockIdx.y * C + (long)vec * 8;
+    dw_store4(os, s[0], s[1], s[2], s[3]);
+    dw_store4(os + 4, s[4], s[5], s[6], s[7]);
+    dw_store4(oq, q[0], q[1], q[2], q[3]);
+    dw_store4(oq + 4, q[4], q[5], q[6], q[7]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Stride-1 pad-1 backward of depthwise conv + BatchNorm in one kernel:
+// k_bn_bwd_dx + k_depthwise_dgrad<1> + k_depthwise_wgrad_part<1> without the
+// dz tensor between them. dz = A*g - B*y + D (g = dout under the mask, A, B,
+// D per channel as k_bn_bwd_dx builds them) is recomputed where it is used.
+//
+// A block is DWB_TH x DWB_TW pixels x DWB_CV 8-channel vectors, one thread
+// per (pixel, vector); the vector is tid % DWB_CV both when staging and when
+// computing, so A, B, D and the nine weight vectors of the thread's channels
+// live in registers. grid.x covers the channel groups, grid.y slices the
+// list of (image, tile) pairs, and a block loops over its tiles:
+//   1. stage dz of the tile plus a one-pixel halo into LDS, rounded to bf16
+//      as the unfused route rounds it; positions outside the image are ZERO
+//      (not D: no dz exists there). LDS is double-buffered, so one barrier
+//      per tile is enough.
+//   2. wgrad: dz of the own pixel (LDS) times x at the nine taps (global,
+//      clamp_tap + zeroing), into 9 x 8 fp32 accumulators that live across
+//      tiles;
+//   3. dx (unless null): the nine neighbouring dz vectors from LDS times the
+//      flipped taps. A tile pixel inside the image is written exactly once.
+// At the end the accumulators are summed over the block's pixels through LDS
+// in fixed order, one tap at a time, and the block writes ONE [9][C] partial
+// in k_depthwise_wgrad_finalize's layout. No atomics.
+// ---------------------------------------------------------------------------
+#define DWB_TH 8
+#define DWB_TW 8
+#define DWB_CV 4
+#define DWB_HW (DWB_TW + 2)                      // halo tile width
+#define DWB_HALO ((DWB_TH + 2) * DWB_HW)         // halo tile pixels
+
+template <int RELU, bool DX>
+__global__ __launch_bounds__(256, 2) DW_NO_PK_F32 void k_depthwise_bwd_bn(
+    const bf16_t* __restrict__ dout, const unsigned char* __restrict__ mask,
+    const bf16_t* __restrict__ y, const bf16_t* __restrict__ x,
+    const bf16_t* __restrict__ w_t, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const float* __restrict__ dbeta, const float* __restrict__ dgamma,
+    bf16_t* __restrict__ dx, float* __restrict__ part, int N, int H, int W_,
+    int C) {
+  static_assert(DWB_TH * DWB_TW * DWB_CV == 256, "one thread per (pixel, vector)");
+  const int vecC = C >> 3;
+  const int tid = threadIdx.x;
+  const int lv = tid % DWB_CV;                   // vector within the group
+  const int lp = tid / DWB_CV;                   // pixel within the tile
+  const int vec = blockIdx.x * DWB_CV + lv;
+  const bool vok = vec < vecC;
+  const long coff = (long)vec * 8;
+
+  float A[8], B[8], D[8];
+  bf16x8 vw[DW_K * DW_K];
+  if (vok) {
+    const float invM = 1.f / (float)((long)N * H * W_);
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = vec * 8 + k;
+      A[k] = gamma[c] * rstd[c];
+      B[k] = A[k] * rstd[c] * dgamma[c] * invM;
+      D[k] = B[k] * mean[c] - A[k] * dbeta[c] * invM;
+    }
+    if (DX) {
+      #pragma unroll
+      for (int t = 0; t < DW_K * DW_K; ++t)
+        vw[t].v = *reinterpret_cast<const uint4*>(w_t + (long)t * C + coff);
+    }
+  }
+
+  float acc[DW_K * DW_K][8];
+  #pragma unroll
+  for (int t = 0; t < DW_K * DW_K; ++t)
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) acc[t][k] = 0.f;
+
+  __shared__ uint4 sdz[2][DWB_HALO * DWB_CV];
+  const int tiles_w = (W_ + DWB_TW - 1) / DWB_TW;
+  const int tiles_h = (H + DWB_TH - 1) / DWB_TH;
+  const int ntiles = N * tiles_h * tiles_w;
+  const int py = lp / DWB_TW, px = lp % DWB_TW;
+  int buf = 0;
+  #pragma unroll 1
+  for (int tile = (int)blockIdx.y; tile < ntiles; tile += (int)gridDim.y, buf ^= 1) {
+    const unsigned tw = (unsigned)tile % (unsigned)tiles_w;
+    const unsigned tt = (unsigned)tile / (unsigned)tiles_w;
+    const int th = (int)(tt % (unsigned)tiles_h);
+    const int n = (int)(tt / (unsigned)tiles_h);
+    const int h0 = th * DWB_TH, w0 = (int)tw * DWB_TW;
+
+    // 1. dz of the tile + halo -> LDS (item = halo pixel * DWB_CV + lv)
+    #pragma unroll 1
+    for (int it = tid; it < DWB_HALO * DWB_CV; it += 256) {
+      const int hp = it / DWB_CV;
+      const int h = h0 - 1 + hp / DWB_HW, w = w0 - 1 + hp % DWB_HW;
+      bf16x8 o;
+      dw_zero(o);
+      if (vok && h >= 0 && h < H && w >= 0 && w < W_) {
+        const int pix = (n * H + h) * W_ + w;
+        bf16x8 vg, vy;
+        vg.v = *reinterpret_cast<const uint4*>(dout + (long)pix * C + coff);
+        vy.v = *reinterpret_cast<const uint4*>(y + (long)pix * C + coff);
+        const unsigned mb = RELU ? mask[(long)pix * vecC + vec] : 0xffu;
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          float g = b2f(vg.h[k]);
+          if (RELU && !((mb >> k) & 1)) g = 0.f;
+          o.h[k] = f2b(A[k] * g - B[k] * b2f(vy.h[k]) + D[k]);
+        }
+      }
+      sdz[buf][it] = o.v;
+    }
+    dw_barrier();
+
+    const int h = h0 + py, w = w0 + px;
+    if (vok && h < H && w < W_) {
+      // 2. wgrad, one tap row of x in flight at a time
+      bf16x8 own;
+      own.v = sdz[buf][((py + 1) * DWB_HW + px + 1) * DWB_CV + lv];
+      float g[8];
+      #pragma unroll
+      for (int k = 0; k < 8; ++k) g[k] = b2f(own.h[k]);
+      #pragma unroll
+      for (int r = 0; r < DW_K; ++r) {
+        const int hh = h - 1 + r;
+        const bool okr = (hh >= 0) && (hh < H);
+        const int hc = clamp_tap(hh, H - 1);
+        bf16x8 vx[DW_K];
+        #pragma unroll
+        for (int c = 0; c < DW_K; ++c) {
+          const int ww = w - 1 + c;
+          const bool ok = okr && (ww >= 0) && (ww < W_);
+          const int wc = clamp_tap(ww, W_ - 1);
+          vx[c].v = *reinterpret_cast<const uint4*>(
+              x + (long)((n * H + hc) * W_ + wc) * C + coff);
+          dw_keep_if(vx[c], ok);
+        }
+        #pragma unroll
+        for (int c = 0; c < DW_K; ++c)
+          #pragma unroll
+          for (int k = 0; k < 8; ++k)
+            acc[r * DW_K + c][k] += g[k] * b2f(vx[c].h[k]);
+        // the next row's loads stay behind this row's FMAs: all nine taps
+        // in flight at once spill
+        asm volatile("" ::: "memory");
+      }
+      // 3. dx[h][w] = sum_{r,c} dz[h + 1 - r][w + 1 - c] * w[r][c]
+      if (DX) {
+        float a[8] = {0};
+        #pragma unroll
+        for (int r = 0; r < DW_K; ++r)
+          #pragma unroll
+          for (int c = 0; c < DW_K; ++c) {
+            keep_packed(vw[r * DW_K + c].v);
+            bf16x8 vd;
+            vd.v = sdz[buf][((py + 2 - r) * DWB_HW + px + 2 - c) * DWB_CV + lv];
+            #pragma unroll
+            for (int k = 0; k < 8; ++k)
+              a[k] += b2f(vd.h[k]) * b2f(vw[r * DW_K + c].h[k]);
+          }
+        bf16x8 o;
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) o.h[k] = f2b(a[k]);
+        *reinterpret_cast<uint4*>(dx + (long)((n * H + h) * W_ + w) * C + coff) = o.v;
+      }
+    }
+  }
+
+  // fold the accumulators over the block's 64 pixels, one tap at a time:
+  // thread (grp, out) sums pixels grp*8 .. grp*8+7 of output out = (lv, k)
+  // in order, then the first 32 threads add the 8 group sums in order
+  __shared__ float red[256 * 8];
+  __shared__ float red2[8][DWB_CV * 8];
+  const int out = tid % (DWB_CV * 8), grp = tid / (DWB_CV * 8);
+  const int ov = out >> 3, ok8 = out & 7;
+  const int ovec = blockIdx.x * DWB_CV + ov;
+  float* pout = part + (long)blockIdx.y * (DW_K * DW_K) * C + (long)ovec * 8 + ok8;
+  #pragma unroll
+  for (int t = 0; t < DW_K * DW_K; ++t) {
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) red[tid * 8 + k] = acc[t][k];
+    dw_barrier();
+    float a = 0.f;
+    #pragma unroll
+    for (int i = 0; i < 8; ++i) a += red[((grp * 8 + i) * DWB_CV + ov) * 8 + ok8];
+    red2[grp][out] = a;
+    dw_barrier();                            // also frees red for the next tap
+    if (grp == 0 && ovec < vecC) {
+      a = red2[0][out];
+      #pragma unroll
+      for (int i = 1; i < 8; ++i) a += red2[i][out];
+      pout[(long)t * C] = a;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host entry points
 // ---------------------------------------------------------------------------
@@ -331,6 +655,82 @@ DDLW_EXPORT int ddlw_depthwise_fwd_ep(const void* x, const void* w_t, void* y,
                        (const bf16_t*)w_t, (bf16_t*)y, (const float*)scale,
                        (const float*)bias, act, N, H, W_, C, Ho, Wo, pad);
   });
+  DDLW_CHECK_LAUNCH();
+}
+
+// number of [C] statistics partial rows the training forward writes for
+// `rows` = N*Ho*Wo (<= DW_MAX_PARTS: they go straight into k_bn_finalize);
+// launches nothing, `stream` is unused (as in ddlw_pw_conv_nparts)
+DDLW_EXPORT int ddlw_depthwise_fwd_stats_nparts(long rows, int C, void* stream) {
+  (void)stream;
+  if (C < 8) return 1;
+  return ColumnGeom(C).capped_slices(rows, DW_MAX_PARTS);
+}
+
+DDLW_EXPORT int ddlw_depthwise_fwd_stats(const void* x, const void* w_t, void* y,
+                                         void* psum, void* psq, int N, int H,
+                                         int W_, int C, int Ho, int Wo,
+                                         int stride, int pad, void* stream) {
+  if (int e = dw_check("depthwise_fwd_stats", C, DW_K, DW_K, stride, pad, H, W_,
+                       Ho, Wo))
+    return e;
+  if (N <= 0) return ddlw_fail("depthwise_fwd_stats", "empty batch");
+  if ((long)N * H * W_ >= (1l << 30) || (long)N * Ho * Wo >= (1l << 30))
+    return ddlw_fail("depthwise_fwd_stats",
+                     "tensor too large for 32-bit pixel indexing");
+  const int nparts = ddlw_depthwise_fwd_stats_nparts((long)N * Ho * Wo, C, nullptr);
+  dim3 grid(ColumnGeom(C).gx, nparts);
+  with_int<1, 2>(stride, [&](auto ST) {
+    hipLaunchKernelGGL((k_depthwise_fwd_stats<decltype(ST)::value>), grid,
+                       dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       (const bf16_t*)w_t, (bf16_t*)y, (float*)psum,
+                       (float*)psq, N, H, W_, C, Ho, Wo, pad);
+  });
+  DDLW_CHECK_LAUNCH();
+}
+
+// number of [9][C] partials of the fused backward: one per persistent block
+// row, at most one per (image, tile) pair
+DDLW_EXPORT int ddlw_depthwise_bwd_bn_nparts(int N, int H, int W_, void* stream) {
+  (void)stream;
+  const long tiles = (long)N * cdiv(H, DWB_TH) * cdiv(W_, DWB_TW);
+  return (int)(tiles < DW_MAX_PARTS ? (tiles > 0 ? tiles : 1) : DW_MAX_PARTS);
+}
+
+// dx may be null (no input gradient wanted). part: [nparts][9][C] fp32
+// scratch, dw: [C][9] fp32.
+DDLW_EXPORT int ddlw_depthwise_bwd_bn(const void* dout, const void* mask,
+                                      const void* y, const void* x,
+                                      const void* w_t, const void* mean,
+                                      const void* rstd, const void* gamma,
+                                      const void* dbeta, const void* dgamma,
+                                      void* dx, void* part, void* dw, int N,
+                                      int H, int W_, int C, int relu,
+                                      void* stream) {
+  if (int e = dw_check("depthwise_bwd_bn", C, DW_K, DW_K, 1, 1, H, W_, H, W_))
+    return e;
+  if (N <= 0) return ddlw_fail("depthwise_bwd_bn", "empty batch");
+  if (relu && !mask) return ddlw_fail("depthwise_bwd_bn", "relu needs the mask");
+  if ((long)N * H * W_ >= (1l << 30))
+    return ddlw_fail("depthwise_bwd_bn",
+                     "tensor too large for 32-bit pixel indexing");
+  const int nparts = ddlw_depthwise_bwd_bn_nparts(N, H, W_, nullptr);
+  dim3 grid((unsigned)cdiv(C >> 3, DWB_CV), nparts);
+  with_int<0, 1>(relu, [&](auto RELU) {
+    with_bool(dx != nullptr, [&](auto DX) {
+      hipLaunchKernelGGL(
+          (k_depthwise_bwd_bn<decltype(RELU)::value, decltype(DX)::value>),
+          grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout,
+          (const unsigned char*)mask, (const bf16_t*)y, (const bf16_t*)x,
+          (const bf16_t*)w_t, (const float*)mean, (const float*)rstd,
+          (const float*)gamma, (const float*)dbeta, (const float*)dgamma,
+          (bf16_t*)dx, (float*)part, N, H, W_, C);
+    });
+  });
+  hipLaunchKernelGGL(k_depthwise_wgrad_finalize,
+                     dim3((C + 31) / 32, DW_K * DW_K), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)part, (float*)dw, C,
+                     nparts);
   DDLW_CHECK_LAUNCH();
 }
 

@@ -10,6 +10,8 @@ batch, the frozen stem (normalize, 3->32 conv, BN, ReLU6) is one kernel too.
 A training-mode block (the fine-tuned suffix) runs its two pointwise stages on
 ``_PwConvBnActFn``: the conv kernel emits the BN statistics from its epilogue
 and the backward runs on the pointwise dgrad and the split-K wgrad kernels.
+Under ``DDLW_DW_TRAIN=1`` the depthwise stage between them runs on
+``_DwConvBnActFn`` the same way, its stride-1 backward in one kernel.
 A marked training stem fed a uint8 batch runs on ``_StemU8BnActFn`` the same
 way, its forward and its weight gradient reading the bytes.
 """
@@ -362,6 +364,106 @@ def pw_conv_bn_train(conv, bn, x: torch.Tensor) -> torch.Tensor:
                                 _ACT[bn.act])
 
 
+# --------------------------------------------------------------------------- #
+# Training-mode block: depthwise conv + BatchNorm stage on one Function
+# --------------------------------------------------------------------------- #
+
+# Off by default, by the project's rule (docs/KERNELS.md, "Depthwise conv +
+# BN, training path"): at batch 64 / 224 the ``fine_tune_at=13`` step ran
+# 1.03x the speed of ``DDLW_DW_TRAIN=0`` on medians in two runs, by more than
+# that contender's spread in one of them (0.151 vs 0.123 ms) and inside it in
+# the other (0.156 vs 0.225 ms).
+_DW_TRAIN_DEFAULT = "0"
+
+
+def dw_train_enabled() -> bool:
+    """The A/B switch of the depthwise training stage, read at call time:
+    ``DDLW_DW_TRAIN=1`` puts the depthwise conv + BN of a fusable training
+    block on ``_DwConvBnActFn``, ``0`` (the default, see above) leaves them
+    on their modules."""
+    return os.environ.get("DDLW_DW_TRAIN", _DW_TRAIN_DEFAULT) != "0"
+
+
+class _DwConvBnActFn(torch.autograd.Function):
+    """depthwise conv3x3 -> BatchNormAct2d of a training-mode block; mirrors
+    ``_PwConvBnActFn``. Forward: the depthwise kernel writes the conv output
+    and its BN statistics partials in one pass. Backward: BN reduce, then at
+    stride 1 one kernel for BN dx + dgrad + wgrad (``depthwise_bwd_bn``, no
+    dz tensor); at stride 2, or when the weight wants no gradient, the three
+    separate kernels, each only as needed. ``binding.dw_train_route`` sends
+    the shapes that did not win by the measurement rule (the forward of the
+    small, launch-bound layers) back to the kernels it replaces."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running_mean, running_var,
+                momentum: float, eps: float, act: int, stride: int, padding: int):
+        x = x.contiguous(memory_format=torch.channels_last)
+        c = weight.shape[0]
+        ho = (x.shape[2] + 2 * padding - 3) // stride + 1
+        wo = (x.shape[3] + 2 * padding - 3) // stride + 1
+        rows = x.shape[0] * ho * wo
+        if binding.dw_train_route("fwd", c, stride, rows):
+            y, ps, pq, nparts = binding.depthwise_fwd_stats(x, weight, stride, padding)
+            mean, rstd = binding.bn_finalize_parts(
+                ps, pq, nparts, rows, c, eps, momentum, running_mean, running_var)
+        else:
+            y = binding.depthwise_fwd(x, weight, stride, padding)
+            mean, rstd = binding.bn_stats(y, eps, momentum, running_mean,
+                                          running_var)
+        out, mask = binding.bn_apply(y, None, mean, rstd, gamma, beta, act)
+        if mask is None:
+            mask = x.new_empty(0, dtype=torch.uint8)
+        ctx.save_for_backward(x, weight, y, mask, mean, rstd, gamma)
+        ctx.relu = bool(act)  # the mask bit means "gradient passes"
+        ctx.stride, ctx.padding = stride, padding
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, y, mask, mean, rstd, gamma = ctx.saved_tensors
+        dout = dout.contiguous(memory_format=torch.channels_last)
+        if dout.dtype != torch.bfloat16:
+            dout = dout.to(torch.bfloat16)
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dbeta, dgamma = binding.bn_bwd_reduce(dout, mask, y, mean, rstd, ctx.relu)
+        dx = dw = None
+        rows = y.shape[0] * y.shape[2] * y.shape[3]
+        if (need_dw and ctx.padding == 1
+                and binding.dw_train_route("bwd", weight.shape[0], ctx.stride, rows)):
+            dx, dw = binding.depthwise_bwd_bn(dout, mask, y, x, weight, mean, rstd,
+                                              gamma, dbeta, dgamma, ctx.relu, need_dx)
+        elif need_dx or need_dw:
+            dz, _ = binding.bn_bwd_dx(dout, mask, y, mean, rstd, gamma, dbeta,
+                                      dgamma, ctx.relu, False)
+            if need_dx:
+                dx = binding.depthwise_dgrad(dz, weight, x.shape, ctx.stride,
+                                             ctx.padding)
+            if need_dw:
+                dw = binding.depthwise_wgrad(dz, x, weight.shape, ctx.stride,
+                                             ctx.padding)
+        if dw is not None:
+            dw = dw.to(weight.dtype)
+        return dx, dw, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def dw_conv_bn_train(conv, bn, x: torch.Tensor) -> torch.Tensor:
+    """One training-mode depthwise conv3x3 + BatchNormAct2d stage on the
+    stage Function; the BN module's bookkeeping is done here as its forward
+    does."""
+    bn.num_batches_tracked += 1
+    w, b = bn.weight, bn.bias
+    if w.dtype != torch.float32:
+        w, b = w.float(), b.float()
+    return _DwConvBnActFn.apply(x, conv.weight, w, b, bn.running_mean,
+                                bn.running_var, bn.momentum, bn.eps,
+                                _ACT[bn.act], conv.stride[0], conv.padding[0])
+
+
+def _dw_trainable(conv) -> bool:
+    return (_is_depthwise3x3(conv) and conv.weight.dtype == torch.bfloat16
+            and dw_train_enabled())
+
+
 def inverted_residual_train_fusable(block, x: torch.Tensor) -> bool:
     """The conditions under which a training-mode block takes the stage
     Function for its pointwise stages: mirrors
@@ -380,11 +482,14 @@ def inverted_residual_train_fusable(block, x: torch.Tensor) -> bool:
 
 def inverted_residual_train_forward(block, x: torch.Tensor) -> torch.Tensor:
     """Expand and project stages on the stage Function, the depthwise conv
-    and its BN on their modules, the residual add eager."""
+    and its BN on theirs under ``DDLW_DW_TRAIN=1`` (else on their modules),
+    the residual add eager."""
     h = x
     for conv, bn in _stages(block):
         if conv.pw_trainable() and bn.training:
             h = pw_conv_bn_train(conv, bn, h)
+        elif bn.training and _dw_trainable(conv):
+            h = dw_conv_bn_train(conv, bn, h)
         else:
             h = bn(conv(h))
     return x + h if block.use_res else h
