@@ -2,7 +2,7 @@
 """Per-kernel fingerprint of the emitted gfx950 device code.
 
 Compiles every ``ddlw_amd/ops/hip/*.hip`` to device-only assembly with the
-library's build flags and prints one ``file kernel sha256`` line per kernel
+library's build flags (each file's own, ``build.compile_flags``) and prints one ``file kernel sha256`` line per kernel
 (function text + its ``.amdhsa_kernel`` descriptor). Host-side refactors must
 leave the listing unchanged: run it on both trees and ``diff`` the outputs.
 
@@ -15,7 +15,7 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent.parent))
-from ddlw_amd.ops.build import FLAGS, HIPCC  # noqa: E402
+from ddlw_amd.ops.build import HIPCC, compile_flags  # noqa: E402
 
 
 def kernels(asm: str) -> dict:
@@ -39,10 +39,9 @@ def kernels(asm: str) -> dict:
 
 def main() -> int:
     root = Path(sys.argv[1] if len(sys.argv) > 1 else Path(__file__).parents[2])
-    flags = [f for f in FLAGS if f != "-shared"]
     total = 0
     for src in sorted((root / "ddlw_amd" / "ops" / "hip").glob("*.hip")):
-        res = subprocess.run([HIPCC, *flags, "--offload-device-only", "-S",
+        res = subprocess.run([HIPCC, *compile_flags(src), "--offload-device-only", "-S",
                               str(src), "-o", "-"], capture_output=True, text=True)
         if res.returncode != 0:
             sys.stderr.write(res.stderr)

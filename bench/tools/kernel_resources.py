@@ -8,6 +8,9 @@ import sys
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent.parent
+sys.path.insert(0, str(REPO))
+from ddlw_amd.ops.build import FILE_FLAGS  # noqa: E402
+
 HIP = sorted((REPO / "ddlw_amd" / "ops" / "hip").glob("*.hip"))
 OUT = REPO / "profiles" / "kernel_resources.md"
 
@@ -25,7 +28,8 @@ def main() -> int:
     for f in HIP:
         res = subprocess.run(
             ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3",
-             "-std=c++17", "-fPIC", "-c", str(f), "-o", "/dev/null",
+             "-std=c++17", "-fPIC", *FILE_FLAGS.get(f.name, []), "-c", str(f),
+             "-o", "/dev/null",
              "-Rpass-analysis=kernel-resource-usage"],
             capture_output=True, text=True)
         cur = {}

@@ -50,6 +50,13 @@ SIGNATURES = {
     "ddlw_bn_bwd_reduce": (_I, [_P] * 7 + [_L, _I, _I, _P]),
     "ddlw_bn_grad_finalize": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "ddlw_bn_bwd_dx": (_I, [_P] * 10 + [_L, _I, _I, _P]),
+    # bn_folded.hip
+    "ddlw_bn_finalize_folded": (_I, [_P] * 4 + [_I] + [_P] * 4
+                                + [_L, _I, _L, _I, _F, _F, _P]),
+    "ddlw_bn_grad_finalize_folded": (_I, [_P] * 4 + [_I, _P, _P, _I, _L, _I, _P]),
+    # weights.hip
+    "ddlw_dgrad_wpack": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ddlw_dgrad_wpack_s2": (_I, [_P, _P, _I, _I, POINTER(c_long), _P]),
     # pool.hip
     "ddlw_maxpool3x3s2_fwd": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),
     "ddlw_maxpool3x3s2_bwd": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),

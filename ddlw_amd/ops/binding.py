@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from .runtime import launch, query
+from .runtime import TICKET_INTS, launch, query, ticket_buffer
 
 
 def _nhwc(t: torch.Tensor) -> torch.Tensor:
@@ -56,16 +56,47 @@ def bn_stats(x: torch.Tensor, eps: float, momentum: float,
     return mean, rstd
 
 
+_FOLD_ABOVE = 512  # partial rows the finalize kernels take directly
+
+
+def _fold_groups(C: int) -> int:
+    """Stage rows G a large partial set is folded to: a chip-filling grid of
+    (ceil(C/32), G) blocks."""
+    return max(8, 512 // max(1, (C + 31) // 32))
+
+
 def _fold_parts(p0: torch.Tensor, p1: torch.Tensor, nparts: int, C: int):
     """Pre-reduce a large pair of [nparts, C] partial arrays to G rows with a
     chip-filling grid: the finalize kernels run ceil(C/32) blocks and would
     serialize a 12k-row partial read on 2 CUs."""
-    if nparts <= 512:
+    if nparts <= _FOLD_ABOVE:
         return p0, p1, nparts
-    G = max(8, 512 // max(1, (C + 31) // 32))
+    G = _fold_groups(C)
     stage = torch.empty(2, G, C, dtype=torch.float32, device=p0.device)
     launch("bn_parts_fold", p0, p1, stage[0], stage[1], nparts, C, G)
     return stage[0], stage[1], G
+
+
+def bn_folded_enabled() -> bool:
+    """``DDLW_BN_FOLDED``, read per call: ``1`` -> a partial set of more than
+    512 rows is folded and finalized in one launch (``hip/bn_folded.hip``);
+    unset / ``0`` -> ``k_bn_parts_fold`` and the finalize kernel, two
+    launches. The results are bit-identical either way. Off by default: a
+    measured loss on the flagship (docs/KERNELS.md, "Measured negative
+    results")."""
+    return os.environ.get("DDLW_BN_FOLDED", "")[:1] == "1"
+
+
+def _folded_args(p0: torch.Tensor, nparts: int, C: int):
+    """(stage [2, G, C], ticket buffer, its length, G) of a folded finalize,
+    or None where the two-launch path runs."""
+    if (nparts <= _FOLD_ABOVE or (C + 31) // 32 > TICKET_INTS
+            or not bn_folded_enabled()):
+        return None
+    G = _fold_groups(C)
+    stage = torch.empty(2, G, C, dtype=torch.float32, device=p0.device)
+    ticket = ticket_buffer(p0.device)
+    return stage, ticket, ticket.numel(), G
 
 
 def bn_finalize_parts(part_sum: torch.Tensor, part_sumsq: torch.Tensor,
@@ -76,6 +107,13 @@ def bn_finalize_parts(part_sum: torch.Tensor, part_sumsq: torch.Tensor,
     dev = part_sum.device
     mean = torch.empty(C, dtype=torch.float32, device=dev)
     rstd = torch.empty(C, dtype=torch.float32, device=dev)
+    folded = _folded_args(part_sum, nparts, C)
+    if folded is not None:
+        stage, ticket, nticket, G = folded
+        launch("bn_finalize_folded", part_sum, part_sumsq, stage, ticket,
+               nticket, mean, rstd, running_mean, running_var, rows, C,
+               nparts, G, eps, momentum)
+        return mean, rstd
     part_sum, part_sumsq, nparts = _fold_parts(part_sum, part_sumsq, nparts, C)
     launch("bn_finalize", part_sum, part_sumsq, mean, rstd, running_mean,
            running_var, rows, C, nparts, eps, momentum)
@@ -86,9 +124,15 @@ def bn_grad_finalize_parts(part_db: torch.Tensor, part_dg: torch.Tensor,
                            nparts: int, C: int):
     """(dbeta, dgamma) from dgrad-epilogue-fused reduce partials."""
     dev = part_db.device
-    part_db, part_dg, nparts = _fold_parts(part_db, part_dg, nparts, C)
     dbeta = torch.empty(C, dtype=torch.float32, device=dev)
     dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+    folded = _folded_args(part_db, nparts, C)
+    if folded is not None:
+        stage, ticket, nticket, G = folded
+        launch("bn_grad_finalize_folded", part_db, part_dg, stage, ticket,
+               nticket, dbeta, dgamma, C, nparts, G)
+        return dbeta, dgamma
+    part_db, part_dg, nparts = _fold_parts(part_db, part_dg, nparts, C)
     launch("bn_grad_finalize", part_db, part_dg, dbeta, dgamma, C, nparts)
     return dbeta, dgamma
 

@@ -100,5 +100,25 @@ def query(name: str, *args):
     return getattr(require_lib(), "ddlw_" + name)(*args)
 
 
+# ints per ticket buffer: one counter per 32 channels, sized for C = 4096
+TICKET_INTS = 4096 // 32
+_tickets = {}
+
+
+def ticket_buffer(device: torch.device) -> torch.Tensor:
+    """The int32 [TICKET_INTS] counter buffer of (device, torch's current
+    stream) for the kernels that elect their last block with a ticket
+    (``hip/bn_folded.hip``). Created zeroed on first use and kept; every
+    kernel leaves it zero, and kernels of one stream are serial, so they
+    share it. It is never zeroed per call: that would be a launch."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(),
+           current_stream_ptr())
+    t = _tickets.get(key)
+    if t is None:
+        t = torch.zeros(TICKET_INTS, dtype=torch.int32, device=device)
+        _tickets[key] = t
+    return t
+
+
 def on_gpu(*tensors: torch.Tensor) -> bool:
     return all(t.is_cuda for t in tensors)
