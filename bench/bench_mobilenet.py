@@ -59,6 +59,13 @@ hand loop — four contenders alternating. The optimizer (``adadelta_step_*``): 
 trainable parameters of ``fine_tune_at=13`` and of the head alone; recorded
 only.
 
+The split-reduction pointwise kernel (``--only-pw-deep``, ``pw_deep*`` rows):
+the deep 7x7 layers frozen (plain ``k_pw_conv`` vs ``k_pw_conv_deep`` at
+mr = 1 and 2), their training directions against what runs today, and the
+frozen forward, the head step and the ``fine_tune_at=13`` step with
+``DDLW_PW_DEEP`` unset / ``0`` / ``1``. Same alternation, same rule
+(``binding.pw_deep_route`` holds the verdicts and the ``mr`` per shape).
+
 Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
 Prints one JSON line per layer shape, a table, and one final JSON line.
 """
@@ -594,6 +601,147 @@ def bench_end_to_end_u8(B, dev, iters, rounds):
     return out
 
 
+# The rows of --only-pw-deep: frozen (batch, H, C, K, act, res) and training
+# (direction, C, K of the conv, H, what the row runs on today by
+# binding.pw_train_route: "lib" or "plain", batch). pw_deep_route does not
+# know the direction, so every GEMM it names is measured in each direction
+# MobileNetV2 runs it in.
+PW_DEEP_FROZEN = [(64, 7, 576, 160, 0, False), (64, 7, 960, 160, 0, True),
+                  (64, 7, 960, 320, 0, False), (16, 7, 576, 160, 0, False),
+                  (16, 7, 960, 160, 0, True), (16, 7, 960, 320, 0, False),
+                  (64, 14, 576, 96, 0, False)]
+PW_DEEP_TRAIN = [("fwd+stats", 960, 160, 7, "lib", 64), ("fwd+stats", 960, 320, 7, "lib", 64),
+                 ("fwd+stats", 576, 160, 7, "plain", 64), ("dgrad", 160, 960, 7, "lib", 64),
+                 ("dgrad", 320, 1280, 7, "lib", 64),
+                 ("fwd+stats", 576, 96, 14, "plain", 64), ("dgrad", 96, 576, 14, "plain", 64),
+                 ("fwd+stats", 960, 160, 7, "plain", 16), ("fwd+stats", 960, 320, 7, "plain", 16),
+                 ("fwd+stats", 576, 160, 7, "plain", 16), ("dgrad", 160, 960, 7, "plain", 16)]
+
+
+def _deep_verdict(samples: dict, replaced: str) -> dict:
+    """Medians of every contender, the spread (max - min) of the one being
+    replaced, and per deep variant whether it beats that one by more than
+    that spread."""
+    old = samples[replaced]
+    m_old = statistics.median(old)
+    spread = max(old) - min(old)
+    rec = {f"ms_{replaced}": round(m_old, 4), f"spread_{replaced}": round(spread, 4)}
+    for name, v in samples.items():
+        if name != replaced:
+            m = statistics.median(v)
+            rec[f"ms_{name}"] = round(m, 4)
+            rec[f"speedup_{name}"] = round(m_old / m, 2)
+            rec[f"win_{name}"] = bool(m_old - m > spread)
+    return rec
+
+
+def bench_pw_deep_frozen(B, H, C, K, act, res, dev, iters, rounds):
+    """One frozen pointwise layer on the plain kernel and on the
+    split-reduction kernel at mr = 1 and 2, all through the same binding
+    body, alternating."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    w = (torch.randn(K, C, 1, 1, device=dev) / C ** 0.5).to(torch.bfloat16)
+    scale, bias = _bn(K, act, dev).folded_scale_bias()
+    r = _cl(torch.randn(B, K, H, H, device=dev).to(torch.bfloat16)) if res else None
+    fns = {name: (lambda mr=mr: binding._pw_conv_fwd(x, w, scale, bias, act, r, None, mr))
+           for name, mr in (("plain", None), ("deep1", 1), ("deep2", 2))}
+    with torch.no_grad():
+        ref = fns["plain"]().float()
+        err = max(((fns[n]().float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
+                  for n in ("deep1", "deep2"))
+        rec = _deep_verdict(time_interleaved(fns, iters, rounds), "plain")
+    M = B * H * H
+    return {"kind": "pw_deep", "shape": f"m{M}_c{C}_k{K}" + ("_res" if res else ""),
+            "M": M, "C": C, "K": K, "rel_err_vs_plain": round(err, 5), **rec}
+
+
+def bench_pw_deep_train(direction, C, K, H, today, B, dev, iters, rounds):
+    """One training direction of the conv C -> K: what runs today (``today``:
+    the library path or the plain kernel) against the split-reduction kernel
+    at mr = 1 and 2. The dgrad contenders rebuild w^T per call, as
+    ``pw_conv_dgrad`` does."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    dy = _cl(torch.randn(B, K, H, H, device=dev).to(torch.bfloat16))
+    w = (torch.randn(K, C, 1, 1, device=dev) / C ** 0.5).to(torch.bfloat16)
+    w = w.contiguous(memory_format=torch.channels_last)
+    rm, rv = torch.zeros(K, device=dev), torch.ones(K, device=dev)
+    M = B * H * H
+    eps, mom = 1e-5, 0.1
+
+    def fwd(stats_fn):
+        y, ps, pq, nparts = stats_fn()
+        return y, binding.bn_finalize_parts(ps, pq, nparts, M, K, eps, mom, rm, rv)
+
+    def fwd_lib():
+        y = F.conv2d(x, w)
+        return y, binding.bn_stats(y, eps, mom, rm, rv)
+
+    if direction == "fwd+stats":
+        fns = {"lib": fwd_lib,
+               "plain": lambda: fwd(lambda: binding._pw_conv_fwd_stats(x, w, None, None, "bench"))}
+        for mr in (1, 2):
+            fns[f"deep{mr}"] = lambda mr=mr: fwd(
+                lambda: binding.pw_conv_deep_fwd_stats(x, w, mr=mr))
+    else:
+        fns = {"lib": lambda: (_conv_backward(dy, x, w, [True, False, False])[0],),
+               "plain": lambda: (binding._pw_conv_fwd(
+                   dy, binding._pw_w2(w).t().contiguous(), None, None, 0, None, None, None),)}
+        for mr in (1, 2):
+            fns[f"deep{mr}"] = lambda mr=mr: (binding.pw_conv_deep_fwd(
+                dy, binding._pw_w2(w).t().contiguous(), mr=mr),)
+    fns = {n: f for n, f in fns.items() if n == today or n.startswith("deep")}
+    with torch.no_grad():
+        ref = fns[today]()[0].float()
+        err = max(((fns[n]()[0].float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
+                  for n in ("deep1", "deep2"))
+        rec = _deep_verdict(time_interleaved(fns, iters, rounds), today)
+    return {"kind": "pw_deep_" + direction, "shape": f"m{M}_c{C}_k{K}", "M": M, "C": C,
+            "K": K, "today": today, "rel_err_vs_today": round(err, 5), **rec}
+
+
+def bench_pw_deep_end_to_end(B, dev, iters, rounds):
+    """The frozen forward, the head-training step and the fine_tune_at=13
+    step with ``DDLW_PW_DEEP`` unset ("default": the measured predicate), ``0``
+    ("off") and ``1`` ("forced"), alternating in one process."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
+    labels = torch.randint(0, 5, (B,), device=dev)
+    os.environ.pop("DDLW_PW_DEEP", None)
+
+    def three(fn):
+        s = time_interleaved({"default": fn, "off": _with_env("DDLW_PW_DEEP", "0", fn),
+                              "forced": _with_env("DDLW_PW_DEEP", "1", fn)}, iters, rounds)
+        return {**_deep_verdict(s, "off"),
+                "not_slower": bool(statistics.median(s["default"]) - statistics.median(s["off"])
+                                   <= max(s["off"]) - min(s["off"]))}
+
+    base = apply_bf16_policy(MobileNetV2().to(dev)).eval()
+
+    def fwd():
+        with torch.no_grad():
+            return base(x)
+
+    out = {"pw_deep_base_fwd": three(fwd)}
+    del base
+    for name, k in (("pw_deep_head_step", None), ("pw_deep_finetune_step_at_13", 13)):
+        kw = {} if k is None else {"fine_tune_at": k}
+        model = apply_bf16_policy(build_model(224, 224, 3, 5, **kw).to(dev)).train()
+        opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4)
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            loss = softmax_cross_entropy(model(x), labels)
+            loss.backward()
+            opt.step()
+            return loss
+
+        out[name] = three(step)
+        del model, opt
+    return out
+
+
 def _stats(samples: dict, B=None) -> dict:
     out = {}
     for k, v in samples.items():
@@ -715,6 +863,8 @@ def main():
                     help="run only the training-stem-from-uint8 stage and step")
     ap.add_argument("--only-dw-train", action="store_true",
                     help="run only the depthwise training stage rows and steps")
+    ap.add_argument("--only-pw-deep", action="store_true",
+                    help="run only the split-reduction pointwise rows and steps")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -722,8 +872,21 @@ def main():
         sys.exit("bench_mobilenet: no GPU (timings are only meaningful on the device)")
     dev = torch.device("cuda:0")
     B = args.batch
-    if args.only_stem_u8_train or args.only_dw_train:
+    if args.only_stem_u8_train or args.only_dw_train or args.only_pw_deep:
         args.skip_layers = args.skip_e2e = args.skip_facade = True
+    pw_deep = {}
+    if args.only_pw_deep:
+        rows = [bench_pw_deep_frozen(*row, dev, args.iters, args.rounds)
+                for row in PW_DEEP_FROZEN]
+        rows += [bench_pw_deep_train(*row, dev, args.iters, args.rounds)
+                 for row in PW_DEEP_TRAIN]
+        for rec in rows:
+            print(json.dumps(rec), flush=True)
+        pw_deep = {"pw_deep_layers": rows,
+                   **bench_pw_deep_end_to_end(B, dev, args.e2e_iters, args.rounds)}
+        for name, r in pw_deep.items():
+            if name != "pw_deep_layers":
+                print(json.dumps({name: r}), flush=True)
     layers = []
     train_layers = []
     stem_train = []
@@ -804,7 +967,7 @@ def main():
     report = {"bench": "mobilenet_v2_frozen", "batch": B, "layers": layers,
               "train_layers": train_layers, "dw_train_layers": dw_train,
               "stem_u8": stem,
-              "stem_u8_train": stem_train, **finetune, **e2e, **facade}
+              "stem_u8_train": stem_train, **finetune, **e2e, **facade, **pw_deep}
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(report, indent=2))
@@ -826,6 +989,7 @@ def main():
         summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
                                            "img_s_unfused", "speedup")}
     summary.update(facade)
+    summary.update({k: v for k, v in pw_deep.items() if k != "pw_deep_layers"})
     print(json.dumps(summary), flush=True)
 
 

@@ -366,7 +366,30 @@ def pw_conv_fwd(x: torch.Tensor, weight: torch.Tensor,
     ``act(conv(x) * scale[k] + bias[k] + res)``. x channels_last bf16
     [N,C,H,W] (or rows [M,C]); weight [K,C,1,1] (or [K,C]); scale/bias fp32
     [K], both or neither; res like the output; act 0 none / 1 ReLU / 2 ReLU6.
-    ``out``: write into this bf16 tensor of the output's shape and layout."""
+    ``out``: write into this bf16 tensor of the output's shape and layout.
+    A shape ``pw_deep_route`` names runs on the split-reduction kernel."""
+    rows, _ = _rows_c(x)
+    return _pw_conv_fwd(x, weight, scale, bias, act, res, out,
+                        pw_deep_route(weight.shape[1], weight.shape[0], rows))
+
+
+def pw_conv_deep_fwd(x: torch.Tensor, weight: torch.Tensor,
+                     scale: Optional[torch.Tensor] = None,
+                     bias: Optional[torch.Tensor] = None, act: int = 0,
+                     res: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None,
+                     mr: Optional[int] = None) -> torch.Tensor:
+    """``pw_conv_fwd`` on the split-reduction kernel (``hip/pointwise_deep.hip``)
+    whatever the route says: same arguments, same result shape. ``mr``: 1 or 2
+    16-row fragments per block tile; ``None`` takes the route's choice, else 2."""
+    rows, _ = _rows_c(x)
+    return _pw_conv_fwd(x, weight, scale, bias, act, res, out,
+                        _pw_deep_mr(mr, weight.shape[1], weight.shape[0], rows))
+
+
+def _pw_conv_fwd(x, weight, scale, bias, act, res, out, mr) -> torch.Tensor:
+    """``pw_conv_fwd`` on the plain kernel (``mr`` None) or the
+    split-reduction one with ``mr`` fragments per tile."""
     K, C = weight.shape[0], weight.shape[1]
     rows, cx = _rows_c(x)
     assert cx == C, f"pw_conv_fwd: x has {cx} channels, weight {C}"
@@ -394,8 +417,12 @@ def pw_conv_fwd(x: torch.Tensor, weight: torch.Tensor,
         res = _nhwc(res)
     if scale is not None:
         scale, bias = _f32c(scale, K), _f32c(bias, K)
-    launch("pw_conv_fwd", _nhwc(x), w2, y, res, scale, bias, int(act), rows, C,
-           K)
+    if mr is None:
+        launch("pw_conv_fwd", _nhwc(x), w2, y, res, scale, bias, int(act), rows,
+               C, K)
+    else:
+        launch("pw_conv_deep_fwd", _nhwc(x), w2, y, res, scale, bias, int(act),
+               rows, C, K, mr)
     return y
 
 
@@ -554,6 +581,57 @@ def pw_train_route(direction: str, C: int, K: int, M: int) -> bool:
     return True
 
 
+# (depth, K) -> (mr, smallest measured M, largest measured M): the rows of the
+# --only-pw-deep table (bench/bench_mobilenet.py) whose median beat the
+# contender they replace by more than its spread in both of two runs.
+_PW_DEEP_MEASURED = {
+    (576, 160): (2, 784, 3136),      # frozen 2.2x, fwd+stats 1.16x
+    (960, 160): (1, 784, 3136),      # frozen 3.0x, fwd+stats 1.7-1.8x, dgrad of 160->960 1.3-2.4x
+    (960, 320): (2, 784, 3136),      # frozen 2.7x, fwd+stats 1.7x
+    (1280, 320): (2, 3136, 3136),    # dgrad of 320->1280 1.2x (mr = 1 loses: 0.81x)
+    # not (576, 96) at 12544 rows: frozen 1.39x and dgrad 1.13x, but fwd+stats
+    # 0.96x, and the route does not know the direction
+}
+
+
+def pw_deep_route(depth: int, K: int, M: int) -> Optional[int]:
+    """The ``mr`` (16-row fragments per block tile) with which the pointwise
+    GEMM of reduction length ``depth`` onto ``K`` output channels over ``M``
+    rows runs on the split-reduction kernel (``hip/pointwise_deep.hip``), or
+    ``None`` for the plain kernel. ``DDLW_PW_DEEP``, read per call: ``0`` ->
+    never; ``1`` -> every shape the kernel takes with ``depth >= 512`` and at
+    most 512 partial rows (what ``bn_finalize_parts`` takes without a fold
+    launch); unset -> the measured rows only, each from its smallest to its
+    largest measured ``M`` (table and rule: docs/KERNELS.md, "Split-reduction
+    pointwise conv")."""
+    if depth < 512 or M <= 0 or not pw_conv_supported(depth, K):
+        return None  # most layers leave here, before the environment is read
+    mode = os.environ.get("DDLW_PW_DEEP", "")[:1]
+    if mode == "0":
+        return None
+    row = _PW_DEEP_MEASURED.get((depth, K))
+    if mode == "1":
+        mr = row[0] if row is not None else 2
+        return mr if -(-M // (16 * mr)) <= _FOLD_ABOVE else None
+    if row is not None and row[1] <= M <= row[2]:
+        return row[0]
+    return None
+
+
+def _pw_deep_mr(mr: Optional[int], depth: int, K: int, M: int) -> int:
+    """``mr`` of an explicit call of the split-reduction kernel."""
+    if mr is None:
+        mr = pw_deep_route(depth, K, M) or 2
+    if mr not in (1, 2):
+        raise ValueError(f"pw_conv_deep: mr must be 1 or 2, got {mr}")
+    return mr
+
+
+@functools.lru_cache(maxsize=512)
+def _pw_deep_nparts(rows: int, mr: int) -> int:
+    return int(query("pw_conv_deep_nparts", rows, mr, None))
+
+
 @functools.lru_cache(maxsize=512)
 def _pw_conv_nparts(rows: int, K: int) -> int:
     return int(query("pw_conv_nparts", rows, K, None))
@@ -592,7 +670,12 @@ def _pw_gemm(x: torch.Tensor, w2: torch.Tensor, res, out, who: str) -> torch.Ten
     if res is not None:
         assert res.shape == y.shape, f"{who}: acc must match the output"
         res = _nhwc(res)
-    launch("pw_conv_fwd", _nhwc(x), w2, y, res, None, None, 0, rows, C, K)
+    mr = pw_deep_route(C, K, rows)
+    if mr is None:
+        launch("pw_conv_fwd", _nhwc(x), w2, y, res, None, None, 0, rows, C, K)
+    else:
+        launch("pw_conv_deep_fwd", _nhwc(x), w2, y, res, None, None, 0, rows,
+               C, K, mr)
     return y
 
 
@@ -607,14 +690,33 @@ def pw_conv_fwd_stats(x: torch.Tensor, weight: torch.Tensor, parts=None):
     of its output from the epilogue: returns ``(y, part_sum, part_sumsq,
     nparts)`` with the partials fp32 ``[nparts, K]``, sums over the bf16
     ``y``, for ``bn_finalize_parts``. ``parts``: a pair of contiguous fp32
-    ``[nparts, K]`` tensors to write into."""
+    ``[nparts, K]`` tensors to write into. A shape ``pw_deep_route`` names
+    runs on the split-reduction kernel, with that kernel's ``nparts``."""
+    rows, _ = _rows_c(x)
+    return _pw_conv_fwd_stats(x, weight, parts,
+                              pw_deep_route(weight.shape[1], weight.shape[0], rows),
+                              "pw_conv_fwd_stats")
+
+
+def pw_conv_deep_fwd_stats(x: torch.Tensor, weight: torch.Tensor, parts=None,
+                           mr: Optional[int] = None):
+    """``pw_conv_fwd_stats`` on the split-reduction kernel whatever the route
+    says: same arguments and returns, one partial row per ``16 * mr`` rows.
+    ``mr`` as in ``pw_conv_deep_fwd``."""
+    rows, _ = _rows_c(x)
+    return _pw_conv_fwd_stats(x, weight, parts,
+                              _pw_deep_mr(mr, weight.shape[1], weight.shape[0], rows),
+                              "pw_conv_deep_fwd_stats")
+
+
+def _pw_conv_fwd_stats(x, weight, parts, mr, who: str):
     w2 = _pw_w2(weight)
     K, C = w2.shape
     rows, cx = _rows_c(x)
-    assert cx == C, f"pw_conv_fwd_stats: x has {cx} channels, weight {C}"
+    assert cx == C, f"{who}: x has {cx} channels, weight {C}"
     if not pw_conv_supported(C, K):
-        raise ValueError(f"pw_conv_fwd_stats: C={C}, K={K} must be multiples of 8")
-    nparts = _pw_conv_nparts(rows, K)
+        raise ValueError(f"{who}: C={C}, K={K} must be multiples of 8")
+    nparts = _pw_conv_nparts(rows, K) if mr is None else _pw_deep_nparts(rows, mr)
     if parts is None:
         both = torch.empty(2, nparts, K, dtype=torch.float32, device=x.device)
         ps, pq = both[0], both[1]
@@ -622,9 +724,12 @@ def pw_conv_fwd_stats(x: torch.Tensor, weight: torch.Tensor, parts=None):
         ps, pq = parts
         for t in (ps, pq):
             assert (t.dtype == torch.float32 and t.is_contiguous()
-                    and tuple(t.shape) == (nparts, K)), "pw_conv_fwd_stats: parts"
-    y = _pw_out(x, rows, K, None, "pw_conv_fwd_stats")
-    launch("pw_conv_fwd_stats", _nhwc(x), w2, y, ps, pq, rows, C, K)
+                    and tuple(t.shape) == (nparts, K)), f"{who}: parts"
+    y = _pw_out(x, rows, K, None, who)
+    if mr is None:
+        launch("pw_conv_fwd_stats", _nhwc(x), w2, y, ps, pq, rows, C, K)
+    else:
+        launch("pw_conv_deep_fwd_stats", _nhwc(x), w2, y, ps, pq, rows, C, K, mr)
     return y, ps, pq, nparts
 
 

@@ -41,6 +41,7 @@ FLAGS = [
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {
     "bn_folded.hip": NO_PK_F32,
+    "pointwise_deep.hip": NO_PK_F32,
     "weights.hip": NO_PK_F32,
 }
 # the host half of a compile does not know the device feature and says so

@@ -70,7 +70,8 @@ def pw_conv_backward(dy, x, weight, need_dx: bool, need_dw: bool):
     k, c = weight.shape[0], weight.shape[1]
     rows = x.shape[0] * x.shape[2] * x.shape[3]
     dx = dw = None
-    lib_dx = need_dx and not binding.pw_train_route("dgrad", c, k, rows)
+    lib_dx = need_dx and not (binding.pw_train_route("dgrad", c, k, rows)
+                              or binding.pw_deep_route(k, c, rows) is not None)
     lib_dw = need_dw and not binding.pw_train_route("wgrad", c, k, rows)
     if need_dx and not lib_dx:
         dx = binding.pw_conv_dgrad(dy, weight, x.shape)
@@ -101,7 +102,8 @@ class _PointwiseFn(torch.autograd.Function):
         ctx.save_for_backward(x, weight)
         k, c = weight.shape[0], weight.shape[1]
         rows = x.shape[0] * x.shape[2] * x.shape[3]
-        if binding.pw_train_route("fwd", c, k, rows):
+        if (binding.pw_train_route("fwd", c, k, rows)
+                or binding.pw_deep_route(c, k, rows) is not None):
             return binding.pw_conv_train_fwd(x, weight)
         return F.conv2d(x, weight.to(x.dtype))
 

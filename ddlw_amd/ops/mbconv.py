@@ -319,7 +319,8 @@ class _PwConvBnActFn(torch.autograd.Function):
         x = x.contiguous(memory_format=torch.channels_last)
         k, c = weight.shape[0], weight.shape[1]
         rows = x.shape[0] * x.shape[2] * x.shape[3]
-        if binding.pw_train_route("fwd", c, k, rows):
+        if (binding.pw_train_route("fwd", c, k, rows)
+                or binding.pw_deep_route(c, k, rows) is not None):
             y, ps, pq, nparts = binding.pw_conv_fwd_stats(x, weight)
             mean, rstd = binding.bn_finalize_parts(
                 ps, pq, nparts, rows, k, eps, momentum, running_mean,
