@@ -66,6 +66,13 @@ frozen forward, the head step and the ``fine_tune_at=13`` step with
 ``DDLW_PW_DEEP`` unset / ``0`` / ``1``. Same alternation, same rule
 (``binding.pw_deep_route`` holds the verdicts and the ``mr`` per shape).
 
+The one-kernel inverted residual (``--only-mbconv-fused``, ``mbconv_fused*``
+rows): every distinct stride-1 expanded block through its module forward,
+``DDLW_MBCONV_FUSED=1`` vs ``=0`` (the three kernels it replaces), then the
+frozen forward and the head step from a uint8 batch with the switch unset /
+``0`` / ``1``. Same alternation, same rule (``binding.mbconv_fused_route``
+holds the verdicts).
+
 Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
 Prints one JSON line per layer shape, a table, and one final JSON line.
 """
@@ -742,6 +749,85 @@ def bench_pw_deep_end_to_end(B, dev, iters, rounds):
     return out
 
 
+# The rows of --only-mbconv-fused: the distinct stride-1 expanded blocks of
+# MobileNetV2 @224 as (H, Cin, Cout); Chid = 6 * Cin.
+MBCONV_FUSED_BLOCKS = [(56, 24, 24), (28, 32, 32), (14, 64, 64), (14, 64, 96),
+                       (14, 96, 96), (7, 160, 160), (7, 160, 320)]
+
+
+def _frozen_block(cin, cout, dev):
+    from ddlw_amd.models.mobilenet_v2 import InvertedResidual
+
+    blk = apply_bf16_policy(InvertedResidual(cin, cout, 1, 6).to(dev)).eval()
+    with torch.no_grad():
+        for m in blk.modules():
+            if isinstance(m, BatchNormAct2d):
+                m.running_mean.uniform_(-0.3, 0.3)
+                m.running_var.uniform_(0.5, 1.5)
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.uniform_(-0.2, 0.2)
+    return blk
+
+
+def bench_mbconv_fused_block(B, H, cin, cout, dev, iters, rounds):
+    """One frozen stride-1 block through ``InvertedResidual.forward``: the
+    one-kernel path (``DDLW_MBCONV_FUSED=1``, "fused") against the three
+    kernels it replaces (``=0``, "three"), alternating."""
+    torch.manual_seed(0)
+    blk = _frozen_block(cin, cout, dev)
+    x = _cl(torch.randn(B, cin, H, H, device=dev).to(torch.bfloat16))
+
+    def fwd():
+        with torch.no_grad():
+            return blk(x)
+
+    fns = {"three": _with_env("DDLW_MBCONV_FUSED", "0", fwd),
+           "fused": _with_env("DDLW_MBCONV_FUSED", "1", fwd)}
+    ref = fns["three"]().float()
+    err = ((fns["fused"]().float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
+    rec = _deep_verdict(time_interleaved(fns, iters, rounds), "three")
+    return {"kind": "mbconv_fused", "shape": f"h{H}_c{cin}_h{6 * cin}_k{cout}",
+            "rows": B * H * H, "Cin": cin, "Chid": 6 * cin, "Cout": cout,
+            "rel_err_vs_three": round(err, 5), **rec}
+
+
+def bench_mbconv_fused_end_to_end(B, dev, iters, rounds):
+    """The frozen forward and the head-training step from a uint8 batch with
+    ``DDLW_MBCONV_FUSED`` unset ("default": the measured predicate), ``0``
+    ("off") and ``1`` ("forced"), alternating in one process."""
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    labels = torch.randint(0, 5, (B,), device=dev)
+    os.environ.pop("DDLW_MBCONV_FUSED", None)
+
+    def three(fn):
+        s = time_interleaved({"default": fn, "off": _with_env("DDLW_MBCONV_FUSED", "0", fn),
+                              "forced": _with_env("DDLW_MBCONV_FUSED", "1", fn)}, iters, rounds)
+        return _deep_verdict(s, "off")
+
+    base = apply_bf16_policy(MobileNetV2().to(dev)).eval()
+
+    def fwd():
+        with torch.no_grad():
+            return base(x)
+
+    out = {"mbconv_fused_base_fwd_u8": three(fwd)}
+    del base
+    model = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    out["mbconv_fused_head_step_u8"] = three(step)
+    return out
+
+
 def _stats(samples: dict, B=None) -> dict:
     out = {}
     for k, v in samples.items():
@@ -865,6 +951,8 @@ def main():
                     help="run only the depthwise training stage rows and steps")
     ap.add_argument("--only-pw-deep", action="store_true",
                     help="run only the split-reduction pointwise rows and steps")
+    ap.add_argument("--only-mbconv-fused", action="store_true",
+                    help="run only the one-kernel inverted residual rows and steps")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -872,9 +960,20 @@ def main():
         sys.exit("bench_mobilenet: no GPU (timings are only meaningful on the device)")
     dev = torch.device("cuda:0")
     B = args.batch
-    if args.only_stem_u8_train or args.only_dw_train or args.only_pw_deep:
+    if (args.only_stem_u8_train or args.only_dw_train or args.only_pw_deep
+            or args.only_mbconv_fused):
         args.skip_layers = args.skip_e2e = args.skip_facade = True
     pw_deep = {}
+    if args.only_mbconv_fused:
+        rows = [bench_mbconv_fused_block(B, *row, dev, args.iters, args.rounds)
+                for row in MBCONV_FUSED_BLOCKS]
+        for rec in rows:
+            print(json.dumps(rec), flush=True)
+        pw_deep = {"mbconv_fused_blocks": rows,
+                   **bench_mbconv_fused_end_to_end(B, dev, args.e2e_iters, args.rounds)}
+        for name, r in pw_deep.items():
+            if name != "mbconv_fused_blocks":
+                print(json.dumps({name: r}), flush=True)
     if args.only_pw_deep:
         rows = [bench_pw_deep_frozen(*row, dev, args.iters, args.rounds)
                 for row in PW_DEEP_FROZEN]
@@ -989,7 +1088,8 @@ def main():
         summary[name] = {k: r[k] for k in ("ms_fused", "ms_unfused", "img_s_fused",
                                            "img_s_unfused", "speedup")}
     summary.update(facade)
-    summary.update({k: v for k, v in pw_deep.items() if k != "pw_deep_layers"})
+    summary.update({k: v for k, v in pw_deep.items()
+                    if k not in ("pw_deep_layers", "mbconv_fused_blocks")})
     print(json.dumps(summary), flush=True)
 
 

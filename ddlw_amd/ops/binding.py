@@ -426,6 +426,103 @@ def _pw_conv_fwd(x, weight, scale, bias, act, res, out, mr) -> torch.Tensor:
     return y
 
 
+# ---- frozen inverted residual in one kernel -------------------------------- #
+
+_MBF_MAX_CIN, _MBF_MAX_COUT = 160, 320
+
+
+def mbconv_fused_supported(Cin: int, Chid: int, Cout: int, stride: int = 1) -> bool:
+    """Shapes ``mbconv_fused_fwd`` takes: stride 1, 16-byte bf16x8 vectors on
+    the three channel axes, an x tile (``Cin <= 160``) and project
+    accumulators (``Cout <= 320``) that fit LDS and registers."""
+    return (stride == 1 and min(Cin, Chid, Cout) > 0
+            and Cin % 8 == 0 and Chid % 8 == 0 and Cout % 8 == 0
+            and Cin <= _MBF_MAX_CIN and Cout <= _MBF_MAX_COUT)
+
+
+# (Cin, Chid, Cout) -> (smallest, largest) measured row count N*H*W of the
+# --only-mbconv-fused table (bench/bench_mobilenet.py) whose median beat the
+# three-kernel path by more than that path's spread, at batch 16, 64 and 256
+# alike (the bounds are the batch-16 and batch-256 row counts; the speedups
+# are those three batches in order). No measured loser: a shape that loses a
+# later measurement leaves this table and is named here with its figures.
+_MBCONV_FUSED_MEASURED = {
+    (24, 144, 24): (50176, 802816),    # 56x56: 1.78x, 1.14x, 1.25x
+    (32, 192, 32): (12544, 200704),    # 28x28: 1.78x, 1.85x, 1.40x
+    (64, 384, 64): (3136, 50176),      # 14x14: 1.77x, 1.87x, 1.70x
+    (64, 384, 96): (3136, 50176),      # 14x14: 1.78x, 1.87x, 1.75x
+    (96, 576, 96): (3136, 50176),      # 14x14: 1.84x, 1.89x, 1.59x
+    (160, 960, 160): (784, 12544),     # 7x7, N workgroups only: 1.29x, 1.29x, 1.50x
+    (160, 960, 320): (784, 12544),     # 7x7: 1.09x, 1.09x, 1.26x
+}
+
+
+def mbconv_fused_route(Cin: int, Chid: int, Cout: int, rows: int) -> bool:
+    """True: a frozen stride-1 expand / depthwise 3x3 / project block over
+    ``rows`` = N*H*W pixels runs on the one-kernel path
+    (``hip/mbconv_fused.hip``); False: on the three kernels it replaces.
+    ``DDLW_MBCONV_FUSED``, read per call: ``0`` -> never; ``1`` -> every
+    supported shape; unset -> the measured winners only, each within its
+    measured row range (table and rule: docs/KERNELS.md, "mbconv_fused.hip")."""
+    if rows <= 0 or not mbconv_fused_supported(Cin, Chid, Cout, 1):
+        return False
+    mode = os.environ.get("DDLW_MBCONV_FUSED", "")[:1]
+    if mode == "0":
+        return False
+    if mode == "1":
+        return True
+    row = _MBCONV_FUSED_MEASURED.get((Cin, Chid, Cout))
+    return row is not None and row[0] <= rows <= row[1]
+
+
+def mbconv_fused_fwd(x: torch.Tensor, w1: torch.Tensor, s1: torch.Tensor,
+                     b1: torch.Tensor, wd: torch.Tensor, s2: torch.Tensor,
+                     b2: torch.Tensor, w3: torch.Tensor, s3: torch.Tensor,
+                     b3: torch.Tensor, res: bool,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A frozen stride-1 inverted residual in one launch:
+    ``relu6(x*w1^T*s1+b1)`` -> ``relu6(dw3x3(.)*s2+b2)`` -> ``(.)*w3^T*s3+b3``
+    ``(+ x)``, the two hidden tensors rounded to bf16 as the three-kernel path
+    rounds them. x channels_last bf16 [N,Cin,H,W]; w1 [Chid,Cin,1,1] or
+    [Chid,Cin]; wd [9,Chid] (tap-major, what ``_depthwise_w_t`` gives) or the
+    conv's [Chid,1,3,3]; w3 [Cout,Chid,1,1] or [Cout,Chid]; s*/b* the folded
+    BN, fp32; ``res`` adds x (``Cin == Cout``). ``out``: write into this bf16
+    channels_last tensor [N,Cout,H,W]."""
+    who = "mbconv_fused_fwd"
+    if x.dim() != 4:
+        raise ValueError(f"{who}: x must be [N,C,H,W], got {tuple(x.shape)}")
+    n, cin, h, w = x.shape
+    if w1.dim() not in (2, 4) or w3.dim() not in (2, 4):
+        raise ValueError(f"{who}: w1 / w3 must be 2-D or 1x1 4-D")
+    chid, cout = w1.shape[0], w3.shape[0]
+    if tuple(w1.shape[1:]) not in ((cin,), (cin, 1, 1)):
+        raise ValueError(f"{who}: w1 is {tuple(w1.shape)}, x has {cin} channels")
+    if tuple(w3.shape[1:]) not in ((chid,), (chid, 1, 1)):
+        raise ValueError(f"{who}: w3 is {tuple(w3.shape)}, hidden width {chid}")
+    if not mbconv_fused_supported(cin, chid, cout, 1):
+        raise ValueError(
+            f"{who}: Cin={cin}, Chid={chid}, Cout={cout} must be multiples of 8"
+            f" with Cin <= {_MBF_MAX_CIN} and Cout <= {_MBF_MAX_COUT}")
+    if res and cin != cout:
+        raise ValueError(f"{who}: the residual needs Cin == Cout, got {cin}, {cout}")
+    if tuple(wd.shape) == (chid, 1, 3, 3):
+        wd = _depthwise_w_t(wd)
+    elif tuple(wd.shape) != (9, chid):
+        raise ValueError(f"{who}: wd is {tuple(wd.shape)}, want (9, {chid})")
+    for name, t in (("x", x), ("w1", w1), ("wd", wd), ("w3", w3)):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{who}: {name} must be bf16, got {t.dtype}")
+    for name, t, c in (("s1", s1, chid), ("b1", b1, chid), ("s2", s2, chid),
+                       ("b2", b2, chid), ("s3", s3, cout), ("b3", b3, cout)):
+        if t.dtype != torch.float32 or t.numel() != c or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous fp32 [{c}], got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    y = _pw_out(x, n * h * w, cout, out, who)
+    launch("mbconv_fused_fwd", _nhwc(x), _pw_w2(w1), s1, b1, wd.contiguous(),
+           s2, b2, _pw_w2(w3), s3, b3, y, n, h, w, cin, chid, cout, int(bool(res)))
+    return y
+
+
 # ---- MobileNetV2 stem from uint8 ------------------------------------------- #
 
 

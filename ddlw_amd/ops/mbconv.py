@@ -6,6 +6,9 @@ epilogue of the conv before it: an expanded block is three kernels
 (pointwise MFMA expand + ReLU6, depthwise + ReLU6, pointwise project +
 residual) instead of conv / bn_apply pairs and an eager add. Fed a uint8
 batch, the frozen stem (normalize, 3->32 conv, BN, ReLU6) is one kernel too.
+A stride-1 expanded block whose shape ``binding.mbconv_fused_route`` accepts
+is ONE kernel (``hip/mbconv_fused.hip``, ``DDLW_MBCONV_FUSED``): the hidden
+tensor lives in LDS only.
 
 A training-mode block (the fine-tuned suffix) runs its two pointwise stages on
 ``_PwConvBnActFn``: the conv kernel emits the BN statistics from its epilogue
@@ -91,9 +94,53 @@ def conv_bn_eval(conv, bn, x: torch.Tensor, res=None) -> torch.Tensor:
     return y if res is None else res + y
 
 
+def _dw_w_t_cached(conv) -> torch.Tensor:
+    """``binding._depthwise_w_t(conv.weight)`` ([9][C], tap-major), cached on
+    the module until the weight mutates or moves (as ``_stem3_packed``)."""
+    w = conv.weight
+    key = (w._version, w.data_ptr(), w.device)
+    cached = getattr(conv, "_dw_w_t_cache", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    w_t = binding._depthwise_w_t(w)
+    conv._dw_w_t_cache = (key, w_t)
+    return w_t
+
+
+def _fused_block_stages(block, x: torch.Tensor):
+    """The (expand, depthwise, project) stages of a frozen block that takes
+    the one-kernel path (``hip/mbconv_fused.hip``), else ``None``: three
+    stages pointwise / depthwise 3x3 stride 1 pad 1 / pointwise with bf16
+    weights, ReLU6 after the first two BNs and none after the third, and a
+    shape ``binding.mbconv_fused_route`` accepts (``DDLW_MBCONV_FUSED``)."""
+    stages = _stages(block)
+    if len(stages) != 3:
+        return None
+    (c1, n1), (c2, n2), (c3, n3) = stages
+    if not (_is_pointwise(c1) and _is_pointwise(c3) and _is_depthwise3x3(c2)
+            and c2.stride == (1, 1)):
+        return None
+    if (n1.act, n2.act, n3.act) != ("relu6", "relu6", "none"):
+        return None
+    if any(c.weight.dtype != torch.bfloat16 for c in (c1, c2, c3)):
+        return None
+    rows = x.shape[0] * x.shape[2] * x.shape[3]
+    if not binding.mbconv_fused_route(c1.in_channels, c1.out_channels,
+                                      c3.out_channels, rows):
+        return None
+    return stages
+
+
 @torch.no_grad()
 def inverted_residual_eval_forward(block, x: torch.Tensor) -> torch.Tensor:
     x = x.contiguous(memory_format=torch.channels_last)
+    fused = _fused_block_stages(block, x)
+    if fused is not None:
+        (c1, n1), (c2, n2), (c3, n3) = fused
+        return binding.mbconv_fused_fwd(
+            x, c1.weight, *n1.folded_scale_bias(), _dw_w_t_cached(c2),
+            *n2.folded_scale_bias(), c3.weight, *n3.folded_scale_bias(),
+            block.use_res)
     stages = _stages(block)
     h = x
     for conv, bn in stages[:-1]:
