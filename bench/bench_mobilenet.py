@@ -68,7 +68,9 @@ frozen forward, the head step and the ``fine_tune_at=13`` step with
 
 The one-kernel inverted residual (``--only-mbconv-fused``, ``mbconv_fused*``
 rows): every distinct stride-1 expanded block through its module forward,
-``DDLW_MBCONV_FUSED=1`` vs ``=0`` (the three kernels it replaces), then the
+``DDLW_MBCONV_FUSED=1`` vs ``=0`` (the three kernels it replaces; the four
+stride-2 blocks under ``DDLW_MBCONV_S2`` and the ``t = 1`` block under
+``DDLW_MBCONV_T1`` the same way), then the
 frozen forward and the head step from a uint8 batch with the switch unset /
 ``0`` / ``1``. Same alternation, same rule (``binding.mbconv_fused_route``
 holds the verdicts).
@@ -753,12 +755,19 @@ def bench_pw_deep_end_to_end(B, dev, iters, rounds):
 # MobileNetV2 @224 as (H, Cin, Cout); Chid = 6 * Cin.
 MBCONV_FUSED_BLOCKS = [(56, 24, 24), (28, 32, 32), (14, 64, 64), (14, 64, 96),
                        (14, 96, 96), (7, 160, 160), (7, 160, 320)]
+# ... then the four stride-2 blocks and the t = 1 block, each on a kernel and
+# a switch of its own, as (input H, Cin, Cout, stride, t, switch)
+MBCONV_S2_T1_BLOCKS = [(112, 16, 24, 2, 6, "DDLW_MBCONV_S2"),
+                       (56, 24, 32, 2, 6, "DDLW_MBCONV_S2"),
+                       (28, 32, 64, 2, 6, "DDLW_MBCONV_S2"),
+                       (14, 96, 160, 2, 6, "DDLW_MBCONV_S2"),
+                       (112, 32, 16, 1, 1, "DDLW_MBCONV_T1")]
 
 
-def _frozen_block(cin, cout, dev):
+def _frozen_block(cin, cout, dev, stride=1, t=6):
     from ddlw_amd.models.mobilenet_v2 import InvertedResidual
 
-    blk = apply_bf16_policy(InvertedResidual(cin, cout, 1, 6).to(dev)).eval()
+    blk = apply_bf16_policy(InvertedResidual(cin, cout, stride, t).to(dev)).eval()
     with torch.no_grad():
         for m in blk.modules():
             if isinstance(m, BatchNormAct2d):
@@ -769,32 +778,37 @@ def _frozen_block(cin, cout, dev):
     return blk
 
 
-def bench_mbconv_fused_block(B, H, cin, cout, dev, iters, rounds):
-    """One frozen stride-1 block through ``InvertedResidual.forward``: the
-    one-kernel path (``DDLW_MBCONV_FUSED=1``, "fused") against the three
-    kernels it replaces (``=0``, "three"), alternating."""
+def bench_mbconv_fused_block(B, H, cin, cout, dev, iters, rounds, stride=1, t=6,
+                             switch="DDLW_MBCONV_FUSED"):
+    """One frozen block through ``InvertedResidual.forward``: the one-kernel
+    path (``switch`` at ``1``, "fused") against the kernels it replaces (at
+    ``0``, "three"; two for the ``t = 1`` block), alternating. ``rows``
+    counts output pixels."""
     torch.manual_seed(0)
-    blk = _frozen_block(cin, cout, dev)
+    blk = _frozen_block(cin, cout, dev, stride, t)
     x = _cl(torch.randn(B, cin, H, H, device=dev).to(torch.bfloat16))
 
     def fwd():
         with torch.no_grad():
             return blk(x)
 
-    fns = {"three": _with_env("DDLW_MBCONV_FUSED", "0", fwd),
-           "fused": _with_env("DDLW_MBCONV_FUSED", "1", fwd)}
+    fns = {"three": _with_env(switch, "0", fwd), "fused": _with_env(switch, "1", fwd)}
     ref = fns["three"]().float()
     err = ((fns["fused"]().float() - ref).abs().max() / (ref.abs().max() + 1e-6)).item()
     rec = _deep_verdict(time_interleaved(fns, iters, rounds), "three")
-    return {"kind": "mbconv_fused", "shape": f"h{H}_c{cin}_h{6 * cin}_k{cout}",
-            "rows": B * H * H, "Cin": cin, "Chid": 6 * cin, "Cout": cout,
+    Ho = (H - 1) // stride + 1
+    return {"kind": "mbconv_fused", "shape": f"h{H}_c{cin}_h{t * cin}_k{cout}_s{stride}",
+            "rows": B * Ho * Ho, "Cin": cin, "Chid": t * cin, "Cout": cout,
             "rel_err_vs_three": round(err, 5), **rec}
 
 
 def bench_mbconv_fused_end_to_end(B, dev, iters, rounds):
     """The frozen forward and the head-training step from a uint8 batch with
     ``DDLW_MBCONV_FUSED`` unset ("default": the measured predicate), ``0``
-    ("off") and ``1`` ("forced"), alternating in one process."""
+    ("off") and ``1`` ("forced"), alternating in one process; then the same
+    two workloads with ``DDLW_MBCONV_S2`` and ``DDLW_MBCONV_T1`` unset
+    ("default"), both ``0`` ("off": the five blocks on the kernels they ran
+    on before) and both ``1`` ("forced")."""
     torch.manual_seed(0)
     u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
     x = u8.permute(0, 3, 1, 2)
@@ -806,13 +820,22 @@ def bench_mbconv_fused_end_to_end(B, dev, iters, rounds):
                               "forced": _with_env("DDLW_MBCONV_FUSED", "1", fn)}, iters, rounds)
         return _deep_verdict(s, "off")
 
+    def both(value, fn):
+        return _with_env("DDLW_MBCONV_S2", value, _with_env("DDLW_MBCONV_T1", value, fn))
+
+    def three_new(fn):
+        s = time_interleaved({"default": fn, "off": both("0", fn), "forced": both("1", fn)},
+                             iters, rounds)
+        return _deep_verdict(s, "off")
+
     base = apply_bf16_policy(MobileNetV2().to(dev)).eval()
 
     def fwd():
         with torch.no_grad():
             return base(x)
 
-    out = {"mbconv_fused_base_fwd_u8": three(fwd)}
+    out = {"mbconv_fused_base_fwd_u8": three(fwd),
+           "mbconv_s2_t1_base_fwd_u8": three_new(fwd)}
     del base
     model = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).train()
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
@@ -825,6 +848,7 @@ def bench_mbconv_fused_end_to_end(B, dev, iters, rounds):
         return loss
 
     out["mbconv_fused_head_step_u8"] = three(step)
+    out["mbconv_s2_t1_head_step_u8"] = three_new(step)
     return out
 
 
@@ -967,6 +991,9 @@ def main():
     if args.only_mbconv_fused:
         rows = [bench_mbconv_fused_block(B, *row, dev, args.iters, args.rounds)
                 for row in MBCONV_FUSED_BLOCKS]
+        rows += [bench_mbconv_fused_block(B, H, cin, cout, dev, args.iters, args.rounds,
+                                          stride, t, switch)
+                 for H, cin, cout, stride, t, switch in MBCONV_S2_T1_BLOCKS]
         for rec in rows:
             print(json.dumps(rec), flush=True)
         pw_deep = {"mbconv_fused_blocks": rows,

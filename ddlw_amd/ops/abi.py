@@ -95,6 +95,8 @@ SIGNATURES = {
     "ddlw_pw_conv_deep_fwd_stats": (_I, [_P] * 5 + [_L, _I, _I, _I, _P]),
     # mbconv_fused.hip
     "ddlw_mbconv_fused_fwd": (_I, [_P] * 11 + [_I] * 7 + [_P]),
+    "ddlw_mbconv_fused_s2_fwd": (_I, [_P] * 11 + [_I] * 6 + [_P]),
+    "ddlw_dwpw_fused_fwd": (_I, [_P] * 8 + [_I] * 6 + [_P]),
     # conv_gemm.hip
     "ddlw_conv_fwd_nparts": (_L, [_I] * 8),
     "ddlw_conv_fwd_igemm": (_I, [_P] * 14 + [_I] * 15 + [_P]),

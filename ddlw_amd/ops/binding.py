@@ -523,6 +523,175 @@ def mbconv_fused_fwd(x: torch.Tensor, w1: torch.Tensor, s1: torch.Tensor,
     return y
 
 
+# ---- frozen stride-2 block and t = 1 block in one kernel each --------------- #
+
+_MBF_S2_MAX_CIN, _DWPW_MAX_C = 96, 64
+
+
+def _route_mode(switch: str, measured: dict, key, rows: int) -> bool:
+    """``0`` -> never; ``1`` -> always; unset -> ``key`` is a measured winner
+    and ``rows`` lies in its measured range. Read per call."""
+    mode = os.environ.get(switch, "")[:1]
+    if mode == "0":
+        return False
+    if mode == "1":
+        return True
+    row = measured.get(key)
+    return row is not None and row[0] <= rows <= row[1]
+
+
+def _fused_block_args(who, x, wd, chid, named_bf16, folds):
+    """The argument checks the one-kernel blocks share: bf16 operands, fp32
+    contiguous folds, ``wd`` as [9, Chid] or the conv's [Chid, 1, 3, 3]
+    (returned tap-major)."""
+    if tuple(wd.shape) == (chid, 1, 3, 3):
+        wd = _depthwise_w_t(wd)
+    elif tuple(wd.shape) != (9, chid):
+        raise ValueError(f"{who}: wd is {tuple(wd.shape)}, want (9, {chid})")
+    for name, t in (("x", x), ("wd", wd), *named_bf16):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{who}: {name} must be bf16, got {t.dtype}")
+    for name, t, c in folds:
+        if t.dtype != torch.float32 or t.numel() != c or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous fp32 [{c}], got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    return wd.contiguous()
+
+
+def _fused_block_out(who, x, shape, out):
+    if out is not None:
+        if tuple(out.shape) != shape:
+            raise ValueError(f"{who}: out is {tuple(out.shape)}, want {shape}")
+        return _nhwc(out)
+    return torch.empty(shape, dtype=torch.bfloat16, device=x.device,
+                       memory_format=torch.channels_last)
+
+
+def mbconv_fused_s2_supported(Cin: int, Chid: int, Cout: int) -> bool:
+    """Shapes ``mbconv_fused_s2_fwd`` takes: 16-byte bf16x8 vectors on the
+    three channel axes, ``Cin <= 96`` (the x halo, ``h1`` and ``h2`` within
+    64 KB of LDS) and ``Cout <= 320``."""
+    return (min(Cin, Chid, Cout) > 0
+            and Cin % 8 == 0 and Chid % 8 == 0 and Cout % 8 == 0
+            and Cin <= _MBF_S2_MAX_CIN and Cout <= _MBF_MAX_COUT)
+
+
+# (Cin, Chid, Cout) -> (smallest, largest) measured OUTPUT row count N*Ho*Wo
+# (batch 16 and batch 256 at 224^2) of the stride-2 rows of the
+# --only-mbconv-fused table (bench/bench_mobilenet.py) whose median beat the
+# three-kernel path by more than that path's spread at batch 16, 64 and 256
+# alike, in every run (rule and figures: docs/KERNELS.md, "k_mbconv_fused_s2";
+# the speedups are those three batches in order, two runs). No measured loser:
+# a shape that loses a later measurement leaves this table and is named here
+# with its figures.
+_MBCONV_S2_MEASURED = {
+    (16, 96, 24): (50176, 802816),     # 112->56: 1.82-1.84x, 1.12-1.13x, 1.45x
+    (24, 144, 32): (12544, 200704),    # 56->28: 1.79-1.82x, 1.79-1.81x, 1.57-1.58x
+    (32, 192, 64): (3136, 50176),      # 28->14: 1.82-1.84x, 1.84-1.85x, 1.81-1.83x
+    (96, 576, 160): (784, 12544),      # 14->7: 1.85-1.86x, 1.84-1.86x, 1.18-1.20x
+}
+
+
+def mbconv_fused_s2_route(Cin: int, Chid: int, Cout: int, rows: int) -> bool:
+    """True: a frozen expand / depthwise 3x3 stride 2 / project block with
+    ``rows`` = N*Ho*Wo OUTPUT pixels runs on ``k_mbconv_fused_s2``; False: on
+    the three kernels it replaces. ``DDLW_MBCONV_S2``, read per call: ``0`` ->
+    never; ``1`` -> every supported shape; unset -> the measured winners only,
+    each within its measured row range."""
+    if rows <= 0 or not mbconv_fused_s2_supported(Cin, Chid, Cout):
+        return False
+    return _route_mode("DDLW_MBCONV_S2", _MBCONV_S2_MEASURED, (Cin, Chid, Cout), rows)
+
+
+def mbconv_fused_s2_fwd(x: torch.Tensor, w1: torch.Tensor, s1: torch.Tensor,
+                        b1: torch.Tensor, wd: torch.Tensor, s2: torch.Tensor,
+                        b2: torch.Tensor, w3: torch.Tensor, s3: torch.Tensor,
+                        b3: torch.Tensor,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A frozen stride-2 inverted residual in one launch: the function of
+    ``mbconv_fused_fwd`` with a stride-2 pad-1 depthwise and no residual, same
+    operands. Returns (or writes into ``out``) bf16 channels_last
+    [N, Cout, (H-1)//2+1, (W-1)//2+1]."""
+    who = "mbconv_fused_s2_fwd"
+    if x.dim() != 4:
+        raise ValueError(f"{who}: x must be [N,C,H,W], got {tuple(x.shape)}")
+    n, cin, h, w = x.shape
+    if w1.dim() not in (2, 4) or w3.dim() not in (2, 4):
+        raise ValueError(f"{who}: w1 / w3 must be 2-D or 1x1 4-D")
+    chid, cout = w1.shape[0], w3.shape[0]
+    if tuple(w1.shape[1:]) not in ((cin,), (cin, 1, 1)):
+        raise ValueError(f"{who}: w1 is {tuple(w1.shape)}, x has {cin} channels")
+    if tuple(w3.shape[1:]) not in ((chid,), (chid, 1, 1)):
+        raise ValueError(f"{who}: w3 is {tuple(w3.shape)}, hidden width {chid}")
+    if not mbconv_fused_s2_supported(cin, chid, cout):
+        raise ValueError(
+            f"{who}: Cin={cin}, Chid={chid}, Cout={cout} must be multiples of 8"
+            f" with Cin <= {_MBF_S2_MAX_CIN} and Cout <= {_MBF_MAX_COUT}")
+    wd = _fused_block_args(who, x, wd, chid, (("w1", w1), ("w3", w3)),
+                           (("s1", s1, chid), ("b1", b1, chid), ("s2", s2, chid),
+                            ("b2", b2, chid), ("s3", s3, cout), ("b3", b3, cout)))
+    y = _fused_block_out(who, x, (n, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), out)
+    launch("mbconv_fused_s2_fwd", _nhwc(x), _pw_w2(w1), s1, b1, wd, s2, b2,
+           _pw_w2(w3), s3, b3, y, n, h, w, cin, chid, cout)
+    return y
+
+
+def dwpw_fused_supported(C: int, Cout: int) -> bool:
+    """Shapes ``dwpw_fused_fwd`` takes: multiples of 8, both at most 64 (one
+    chunk of channels, at most two output pairs)."""
+    return (min(C, Cout) > 0 and C % 8 == 0 and Cout % 8 == 0
+            and C <= _DWPW_MAX_C and Cout <= _DWPW_MAX_C)
+
+
+# (C, Cout) -> (smallest, largest) measured row count N*H*W, as above, for the
+# t = 1 block (docs/KERNELS.md, "k_dwpw_fused"). No measured loser.
+_DWPW_MEASURED = {
+    (32, 16): (200704, 3211264),       # 112x112: 1.61-1.66x, 1.39-1.40x, 1.44x
+}
+
+
+def dwpw_fused_route(C: int, Cout: int, rows: int) -> bool:
+    """True: a frozen ``t = 1`` block (depthwise 3x3 stride 1 / project) over
+    ``rows`` = N*H*W pixels runs on ``k_dwpw_fused``; False: on the two
+    kernels it replaces. ``DDLW_MBCONV_T1``, read per call, as
+    ``mbconv_fused_s2_route`` reads its switch."""
+    if rows <= 0 or not dwpw_fused_supported(C, Cout):
+        return False
+    return _route_mode("DDLW_MBCONV_T1", _DWPW_MEASURED, (C, Cout), rows)
+
+
+def dwpw_fused_fwd(x: torch.Tensor, wd: torch.Tensor, s2: torch.Tensor,
+                   b2: torch.Tensor, w3: torch.Tensor, s3: torch.Tensor,
+                   b3: torch.Tensor, res: bool,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A frozen ``t = 1`` inverted residual in one launch:
+    ``relu6(dw3x3(x)*s2+b2)`` (stride 1, pad 1, rounded to bf16 as
+    ``depthwise_fwd_ep`` rounds it) -> ``(.)*w3^T*s3+b3 (+ x)``. x
+    channels_last bf16 [N,C,H,W]; wd [9,C] (tap-major) or the conv's
+    [C,1,3,3]; w3 [Cout,C,1,1] or [Cout,C]; s*/b* the folded BN, fp32;
+    ``res`` adds x (``C == Cout``). ``out``: write into this bf16
+    channels_last tensor [N,Cout,H,W]."""
+    who = "dwpw_fused_fwd"
+    if x.dim() != 4:
+        raise ValueError(f"{who}: x must be [N,C,H,W], got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    if w3.dim() not in (2, 4) or tuple(w3.shape[1:]) not in ((c,), (c, 1, 1)):
+        raise ValueError(f"{who}: w3 is {tuple(w3.shape)}, x has {c} channels")
+    cout = w3.shape[0]
+    if not dwpw_fused_supported(c, cout):
+        raise ValueError(f"{who}: C={c}, Cout={cout} must be multiples of 8, at"
+                         f" most {_DWPW_MAX_C}")
+    if res and c != cout:
+        raise ValueError(f"{who}: the residual needs C == Cout, got {c}, {cout}")
+    wd = _fused_block_args(who, x, wd, c, (("w3", w3),),
+                           (("s2", s2, c), ("b2", b2, c), ("s3", s3, cout),
+                            ("b3", b3, cout)))
+    y = _fused_block_out(who, x, (n, cout, h, w), out)
+    launch("dwpw_fused_fwd", _nhwc(x), wd, s2, b2, _pw_w2(w3), s3, b3, y, n, h, w,
+           c, cout, int(bool(res)))
+    return y
+
+
 # ---- MobileNetV2 stem from uint8 ------------------------------------------- #
 
 

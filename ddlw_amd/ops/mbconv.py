@@ -9,6 +9,9 @@ batch, the frozen stem (normalize, 3->32 conv, BN, ReLU6) is one kernel too.
 A stride-1 expanded block whose shape ``binding.mbconv_fused_route`` accepts
 is ONE kernel (``hip/mbconv_fused.hip``, ``DDLW_MBCONV_FUSED``): the hidden
 tensor lives in LDS only.
+A stride-2 expanded block (``binding.mbconv_fused_s2_route``,
+``DDLW_MBCONV_S2``) and the ``t = 1`` block (``binding.dwpw_fused_route``,
+``DDLW_MBCONV_T1``) have a kernel each in the same file.
 
 A training-mode block (the fine-tuned suffix) runs its two pointwise stages on
 ``_PwConvBnActFn``: the conv kernel emits the BN statistics from its epilogue
@@ -109,24 +112,46 @@ def _dw_w_t_cached(conv) -> torch.Tensor:
 
 def _fused_block_stages(block, x: torch.Tensor):
     """The (expand, depthwise, project) stages of a frozen block that takes
-    the one-kernel path (``hip/mbconv_fused.hip``), else ``None``: three
-    stages pointwise / depthwise 3x3 stride 1 pad 1 / pointwise with bf16
-    weights, ReLU6 after the first two BNs and none after the third, and a
-    shape ``binding.mbconv_fused_route`` accepts (``DDLW_MBCONV_FUSED``)."""
+    a one-kernel path (``hip/mbconv_fused.hip``), else ``None``: three
+    stages pointwise / depthwise 3x3 pad 1 / pointwise with bf16 weights,
+    ReLU6 after the first two BNs and none after the third, and a shape that
+    ``binding.mbconv_fused_route`` (stride 1, ``DDLW_MBCONV_FUSED``) or
+    ``binding.mbconv_fused_s2_route`` (stride 2, ``DDLW_MBCONV_S2``) accepts."""
     stages = _stages(block)
     if len(stages) != 3:
         return None
     (c1, n1), (c2, n2), (c3, n3) = stages
-    if not (_is_pointwise(c1) and _is_pointwise(c3) and _is_depthwise3x3(c2)
-            and c2.stride == (1, 1)):
+    if not (_is_pointwise(c1) and _is_pointwise(c3) and _is_depthwise3x3(c2)):
         return None
     if (n1.act, n2.act, n3.act) != ("relu6", "relu6", "none"):
         return None
     if any(c.weight.dtype != torch.bfloat16 for c in (c1, c2, c3)):
         return None
+    chans = (c1.in_channels, c1.out_channels, c3.out_channels)
+    if c2.stride == (2, 2):
+        rows = x.shape[0] * ((x.shape[2] - 1) // 2 + 1) * ((x.shape[3] - 1) // 2 + 1)
+        return stages if binding.mbconv_fused_s2_route(*chans, rows) else None
     rows = x.shape[0] * x.shape[2] * x.shape[3]
-    if not binding.mbconv_fused_route(c1.in_channels, c1.out_channels,
-                                      c3.out_channels, rows):
+    return stages if binding.mbconv_fused_route(*chans, rows) else None
+
+
+def _fused_t1_stages(block, x: torch.Tensor):
+    """The (depthwise, project) stages of a frozen ``t = 1`` block that takes
+    ``k_dwpw_fused``, else ``None``: depthwise 3x3 stride 1 pad 1 + ReLU6,
+    pointwise with no activation, bf16 weights, and a shape
+    ``binding.dwpw_fused_route`` accepts (``DDLW_MBCONV_T1``)."""
+    stages = _stages(block)
+    if len(stages) != 2:
+        return None
+    (c2, n2), (c3, n3) = stages
+    if not (_is_depthwise3x3(c2) and c2.stride == (1, 1) and _is_pointwise(c3)):
+        return None
+    if (n2.act, n3.act) != ("relu6", "none"):
+        return None
+    if any(c.weight.dtype != torch.bfloat16 for c in (c2, c3)):
+        return None
+    rows = x.shape[0] * x.shape[2] * x.shape[3]
+    if not binding.dwpw_fused_route(c3.in_channels, c3.out_channels, rows):
         return None
     return stages
 
@@ -137,10 +162,17 @@ def inverted_residual_eval_forward(block, x: torch.Tensor) -> torch.Tensor:
     fused = _fused_block_stages(block, x)
     if fused is not None:
         (c1, n1), (c2, n2), (c3, n3) = fused
-        return binding.mbconv_fused_fwd(
-            x, c1.weight, *n1.folded_scale_bias(), _dw_w_t_cached(c2),
-            *n2.folded_scale_bias(), c3.weight, *n3.folded_scale_bias(),
-            block.use_res)
+        args = (x, c1.weight, *n1.folded_scale_bias(), _dw_w_t_cached(c2),
+                *n2.folded_scale_bias(), c3.weight, *n3.folded_scale_bias())
+        if c2.stride == (2, 2):
+            return binding.mbconv_fused_s2_fwd(*args)
+        return binding.mbconv_fused_fwd(*args, block.use_res)
+    fused = _fused_t1_stages(block, x)
+    if fused is not None:
+        (c2, n2), (c3, n3) = fused
+        return binding.dwpw_fused_fwd(
+            x, _dw_w_t_cached(c2), *n2.folded_scale_bias(), c3.weight,
+            *n3.folded_scale_bias(), block.use_res)
     stages = _stages(block)
     h = x
     for conv, bn in stages[:-1]:
