@@ -75,6 +75,13 @@ frozen forward and the head step from a uint8 batch with the switch unset /
 ``0`` / ``1``. Same alternation, same rule (``binding.mbconv_fused_route``
 holds the verdicts).
 
+The fused tail (``--only-tail-gap``, ``tail_gap*`` rows): the 320 -> 1280 conv
++ BN + ReLU6 + global average pool at batch 16 / 64 / 256, ``DDLW_TAIL_GAP=1``
+(``k_pw_conv_gap``, also at 1 / 2 / 4 / 8 images per workgroup) vs ``=0``
+(``k_pw_conv`` + ``k_gap_fwd``), then the frozen model forward and the head
+step from a uint8 batch with the switch unset / ``0`` / ``1``. Same
+alternation, same rule (``binding.pw_gap_route`` holds the verdicts).
+
 Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
 Prints one JSON line per layer shape, a table, and one final JSON line.
 """
@@ -852,6 +859,78 @@ def bench_mbconv_fused_end_to_end(B, dev, iters, rounds):
     return out
 
 
+# The rows of --only-tail-gap: the 320 -> 1280 tail + global average pool of
+# MobileNetV2 @224 (7x7) at these batches.
+TAIL_GAP_BATCHES = [16, 64, 256]
+
+
+def bench_tail_gap_layer(B, dev, iters, rounds, H=7, C=320, K=1280):
+    """The frozen tail conv + BN + ReLU6 + GAP through
+    ``mbconv.conv_bn_gap_eval``: ``DDLW_TAIL_GAP=0`` ("pair": ``k_pw_conv`` +
+    ``k_gap_fwd``) against ``=1`` ("fused": ``k_pw_conv_gap`` with the host's
+    images-per-workgroup choice), and the kernel at imgs = 1, 2, 4, 8,
+    alternating."""
+    from ddlw_amd.ops import mbconv
+
+    torch.manual_seed(0)
+    conv = Conv2d(C, K, 1, bias=False).to(dev).to(torch.bfloat16).eval()
+    bn = _bn(K, 2, dev)
+    scale, bias = bn.folded_scale_bias()
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+
+    def run():
+        with torch.no_grad():
+            return mbconv.conv_bn_gap_eval(conv, bn, x)
+
+    fns = {"pair": _with_env("DDLW_TAIL_GAP", "0", run),
+           "fused": _with_env("DDLW_TAIL_GAP", "1", run)}
+    for imgs in (1, 2, 4, 8):
+        fns[f"imgs{imgs}"] = (lambda imgs=imgs: binding.pw_conv_gap_fwd(
+            x, conv.weight, scale, bias, 2, imgs=imgs))
+    ref = fns["pair"]()
+    equal = all(torch.equal(fn(), ref) for name, fn in fns.items() if name != "pair")
+    rec = _deep_verdict(time_interleaved(fns, iters, rounds), "pair")
+    return {"kind": "tail_gap", "shape": f"n{B}_hw{H * H}_c{C}_k{K}", "N": B,
+            "imgs_host": binding._pw_gap_imgs(B, K, x.device), "bit_equal": equal, **rec}
+
+
+def bench_tail_gap_end_to_end(B, dev, iters, rounds):
+    """The frozen forward (``build_model`` in eval mode: base, pool, head) and
+    the head-training step from a uint8 batch with ``DDLW_TAIL_GAP`` unset
+    ("default": the measured table), ``0`` ("off") and ``1`` ("forced"),
+    alternating in one process."""
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    labels = torch.randint(0, 5, (B,), device=dev)
+    os.environ.pop("DDLW_TAIL_GAP", None)
+
+    def three(fn):
+        s = time_interleaved({"default": fn, "off": _with_env("DDLW_TAIL_GAP", "0", fn),
+                              "forced": _with_env("DDLW_TAIL_GAP", "1", fn)}, iters, rounds)
+        return _deep_verdict(s, "off")
+
+    model = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).eval()
+
+    def fwd():
+        with torch.no_grad():
+            return model(x)
+
+    out = {"tail_gap_model_fwd_u8": three(fwd)}
+    model.train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    out["tail_gap_head_step_u8"] = three(step)
+    return out
+
+
 def _stats(samples: dict, B=None) -> dict:
     out = {}
     for k, v in samples.items():
@@ -977,6 +1056,8 @@ def main():
                     help="run only the split-reduction pointwise rows and steps")
     ap.add_argument("--only-mbconv-fused", action="store_true",
                     help="run only the one-kernel inverted residual rows and steps")
+    ap.add_argument("--only-tail-gap", action="store_true",
+                    help="run only the fused tail conv + GAP rows and steps")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -985,9 +1066,20 @@ def main():
     dev = torch.device("cuda:0")
     B = args.batch
     if (args.only_stem_u8_train or args.only_dw_train or args.only_pw_deep
-            or args.only_mbconv_fused):
+            or args.only_mbconv_fused or args.only_tail_gap):
         args.skip_layers = args.skip_e2e = args.skip_facade = True
     pw_deep = {}
+    if args.only_tail_gap:
+        # the pair is tens of microseconds: ten times the calls per round
+        rows = [bench_tail_gap_layer(b, dev, args.iters * 10, args.rounds)
+                for b in TAIL_GAP_BATCHES]
+        for rec in rows:
+            print(json.dumps(rec), flush=True)
+        pw_deep = {"tail_gap_layers": rows,
+                   **bench_tail_gap_end_to_end(B, dev, args.e2e_iters, args.rounds)}
+        for name, r in pw_deep.items():
+            if name != "tail_gap_layers":
+                print(json.dumps({name: r}), flush=True)
     if args.only_mbconv_fused:
         rows = [bench_mbconv_fused_block(B, *row, dev, args.iters, args.rounds)
                 for row in MBCONV_FUSED_BLOCKS]
@@ -1116,7 +1208,8 @@ def main():
                                            "img_s_unfused", "speedup")}
     summary.update(facade)
     summary.update({k: v for k, v in pw_deep.items()
-                    if k not in ("pw_deep_layers", "mbconv_fused_blocks")})
+                    if k not in ("pw_deep_layers", "mbconv_fused_blocks",
+                                 "tail_gap_layers")})
     print(json.dumps(summary), flush=True)
 
 

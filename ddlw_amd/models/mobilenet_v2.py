@@ -55,6 +55,9 @@ def _pointwise(in_ch: int, out_ch: int) -> Conv2d:
     return conv
 
 
+_POOL = GlobalAvgPool2d()  # stateless: the pool of ``forward(x, pooled=True)``
+
+
 class InvertedResidual(nn.Module):
     def __init__(self, in_ch: int, out_ch: int, stride: int, expand: int):
         super().__init__()
@@ -168,7 +171,11 @@ class MobileNetV2(nn.Module):
         with torch.no_grad():
             return mbconv.normalize_u8_input(x, self.features[0].weight), 0
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, pooled: bool = False) -> torch.Tensor:
+        """``pooled=True`` returns the N x 1280 global-average-pooled features
+        (``GlobalAvgPool2d`` of the plain result) on every branch; on the
+        frozen-fold branch the tail conv and the pool may then be one kernel
+        (``mbconv.conv_bn_gap_eval``)."""
         x, start = self.stem_entry(x)
         n = len(self.features)
         tail_conv, tail_bn = self.features[n - 3], self.features[n - 2]
@@ -178,14 +185,16 @@ class MobileNetV2(nn.Module):
             # conv + BN + ReLU6 is one pointwise kernel as well
             for m in self.features[start: n - 3]:
                 x = m(x)
-            return mbconv.conv_bn_eval(
-                tail_conv, tail_bn,
-                x.contiguous(memory_format=torch.channels_last))
+            x = x.contiguous(memory_format=torch.channels_last)
+            if pooled:
+                return mbconv.conv_bn_gap_eval(tail_conv, tail_bn, x)
+            return mbconv.conv_bn_eval(tail_conv, tail_bn, x)
         if start == 0:
-            return self.features(x)
-        for m in self.features[start:]:
-            x = m(x)
-        return x
+            x = self.features(x)
+        else:
+            for m in self.features[start:]:
+                x = m(x)
+        return _POOL(x) if pooled else x
 
 
 class FrozenBase(nn.Module):
@@ -250,10 +259,14 @@ class FrozenBase(nn.Module):
                 m.eval()
         return self
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, pooled: bool = False) -> torch.Tensor:
+        """``pooled=True`` (a ``MobileNetV2`` base): the global-average-pooled
+        features. Fully frozen, the base pools itself (``MobileNetV2.forward``);
+        with a trainable suffix the module path pools, so autograd sees what
+        it saw."""
         if self._fully_frozen():
             with torch.no_grad():
-                return self.base(x)
+                return self.base(x, pooled=True) if pooled else self.base(x)
         feats = self.base.features
         start = 0
         if x.dtype == torch.uint8:
@@ -271,7 +284,7 @@ class FrozenBase(nn.Module):
                 x = m(x)
         for m in feats[max(start, self._split):]:
             x = m(x)
-        return x
+        return _POOL(x) if pooled else x
 
 
 class TransferModel(nn.Module):
@@ -301,8 +314,13 @@ class TransferModel(nn.Module):
             spec[1]["fine_tune_at"] = fine_tune_at
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = self.base(x)
-        x = self.global_average_pooling(x)  # fused GAP -> (N, C)
+        if (type(self.global_average_pooling) is GlobalAvgPool2d
+                and isinstance(self.base.base, MobileNetV2)):
+            # the stock pool: the base pools, and a frozen one may fuse its
+            # tail conv with the pool (ops/mbconv.py, ``conv_bn_gap_eval``)
+            x = self.base(x, pooled=True)
+        else:
+            x = self.global_average_pooling(self.base(x))  # fused GAP -> (N, C)
         x = self.dropout(x)
         return self.classifier(x.to(self.classifier.weight.dtype))
 

@@ -93,6 +93,8 @@ SIGNATURES = {
     "ddlw_pw_conv_deep_fwd": (_I, [_P] * 6 + [_I, _L, _I, _I, _I, _P]),
     "ddlw_pw_conv_deep_nparts": (_I, [_L, _I, _P]),
     "ddlw_pw_conv_deep_fwd_stats": (_I, [_P] * 5 + [_L, _I, _I, _I, _P]),
+    # pointwise_gap.hip
+    "ddlw_pw_conv_gap_fwd": (_I, [_P] * 5 + [_I] * 6 + [_P]),
     # mbconv_fused.hip
     "ddlw_mbconv_fused_fwd": (_I, [_P] * 11 + [_I] * 7 + [_P]),
     "ddlw_mbconv_fused_s2_fwd": (_I, [_P] * 11 + [_I] * 6 + [_P]),

@@ -692,6 +692,102 @@ def dwpw_fused_fwd(x: torch.Tensor, wd: torch.Tensor, s2: torch.Tensor,
     return y
 
 
+# ---- frozen tail: pointwise conv + BN + activation + GAP in one kernel ------- #
+
+_PW_GAP_MAX_C = 320
+
+
+def pw_conv_gap_supported(C: int, K: int) -> bool:
+    """Shapes ``pw_conv_gap_fwd`` takes: 16-byte bf16x8 vectors on both
+    channel axes and a weight slab that fits the registers (``C <= 320``)."""
+    return 8 <= C <= _PW_GAP_MAX_C and K > 0 and C % 8 == 0 and K % 8 == 0
+
+
+# (C, K, HW) -> (smallest, largest) measured batch N of the --only-tail-gap
+# table (bench/bench_mobilenet.py) whose median beat ``pw_conv_fwd`` +
+# ``gap_fwd`` by more than that pair's spread in both of two runs (rule and
+# figures: docs/KERNELS.md, "pointwise_gap.hip").
+_PW_GAP_MEASURED = {
+    (320, 1280, 49): (16, 256),        # MobileNetV2 tail @224: 1.71-1.77x, 1.89-1.90x, 1.73-1.74x
+}
+
+
+def pw_gap_route(C: int, K: int, HW: int, N: int) -> bool:
+    """True: a frozen 1x1 conv C -> K + BN + activation over ``N`` images of
+    ``HW`` pixels whose only reader is the global average pool runs on
+    ``k_pw_conv_gap`` (``hip/pointwise_gap.hip``); False: on ``pw_conv_fwd``
+    and ``gap_fwd``. ``DDLW_TAIL_GAP``, read per call: ``0`` -> never; ``1``
+    -> every supported shape; unset -> the measured winners only, each
+    within its measured batch range."""
+    if N <= 0 or HW <= 0 or not pw_conv_gap_supported(C, K):
+        return False
+    return _route_mode("DDLW_TAIL_GAP", _PW_GAP_MEASURED, (C, K, HW), N)
+
+
+@functools.lru_cache(maxsize=8)
+def _cu_count(index: int) -> int:
+    return torch.cuda.get_device_properties(index).multi_processor_count
+
+
+def _pw_gap_imgs(N: int, K: int, device: torch.device) -> int:
+    """Images per workgroup: the larger of 4 and 2 that still leaves a
+    workgroup for every second CU, else 1. Measured at 7x7, 320 -> 1280
+    (docs/KERNELS.md, "pointwise_gap.hip"): 4 is the fastest at batch 64 (160
+    workgroups on 256 CUs) and 256, 1 and 2 tie at batch 16, and 8 loses to 4
+    everywhere (the weight slab is amortized by then; fewer workgroups only
+    lengthen the tail)."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    cus, ktiles = _cu_count(index), -(-K // 128)
+    for imgs in (4, 2):
+        if 2 * -(-N // imgs) * ktiles >= cus:
+            return imgs
+    return 1
+
+
+def pw_conv_gap_fwd(x: torch.Tensor, weight: torch.Tensor,
+                    scale: Optional[torch.Tensor] = None,
+                    bias: Optional[torch.Tensor] = None, act: int = 0,
+                    out: Optional[torch.Tensor] = None,
+                    imgs: Optional[int] = None) -> torch.Tensor:
+    """``gap_fwd(pw_conv_fwd(x, weight, scale, bias, act))`` in one launch,
+    bit for bit, without the [N,K,H,W] tensor: 1x1 stride-1 conv, folded BN,
+    activation (0 none / 1 ReLU / 2 ReLU6), rounding to bf16, then the mean
+    over H*W. x channels_last bf16 [N,C,H,W]; weight [K,C,1,1] or [K,C];
+    scale/bias fp32 [K], both or neither. Returns (or writes into ``out``)
+    bf16 [N,K]. ``imgs``: consecutive images per workgroup; ``None`` takes
+    ``_pw_gap_imgs``'s choice."""
+    who = "pw_conv_gap_fwd"
+    if x.dim() != 4:
+        raise ValueError(f"{who}: x must be [N,C,H,W], got {tuple(x.shape)}")
+    n, c, h, w_ = x.shape
+    if weight.dim() not in (2, 4) or tuple(weight.shape[1:]) not in ((c,), (c, 1, 1)):
+        raise ValueError(f"{who}: weight is {tuple(weight.shape)}, x has {c} channels")
+    K = weight.shape[0]
+    if not pw_conv_gap_supported(c, K):
+        raise ValueError(f"{who}: C={c}, K={K} must be multiples of 8 with "
+                         f"8 <= C <= {_PW_GAP_MAX_C}")
+    if h * w_ < 1:
+        raise ValueError(f"{who}: empty feature map {h}x{w_}")
+    if (scale is None) != (bias is None):
+        raise ValueError(f"{who}: scale and bias come together")
+    if scale is not None:
+        scale, bias = _f32c(scale, K), _f32c(bias, K)
+    if out is not None:
+        if (tuple(out.shape) != (n, K) or out.dtype != torch.bfloat16
+                or not out.is_contiguous()):
+            raise ValueError(f"{who}: out must be contiguous bf16 {(n, K)}")
+        p = out
+    else:
+        p = torch.empty((n, K), dtype=torch.bfloat16, device=x.device)
+    if imgs is None:
+        imgs = _pw_gap_imgs(n, K, x.device)
+    elif imgs < 1:
+        raise ValueError(f"{who}: imgs must be at least 1, got {imgs}")
+    launch("pw_conv_gap_fwd", _nhwc(x), _pw_w2(weight), p, scale, bias, int(act),
+           n, h * w_, c, K, int(imgs))
+    return p
+
+
 # ---- MobileNetV2 stem from uint8 ------------------------------------------- #
 
 

@@ -97,6 +97,21 @@ def conv_bn_eval(conv, bn, x: torch.Tensor, res=None) -> torch.Tensor:
     return y if res is None else res + y
 
 
+def conv_bn_gap_eval(conv, bn, x: torch.Tensor) -> torch.Tensor:
+    """A frozen conv + BatchNormAct2d stage whose only reader is the global
+    average pool, as [N, K] pooled features: one kernel
+    (``hip/pointwise_gap.hip``) when ``binding.pw_gap_route`` takes the shape
+    (``DDLW_TAIL_GAP``), else ``conv_bn_eval`` and ``binding.gap_fwd``. The
+    two are bit-equal."""
+    n, _, h, w = x.shape
+    if (_is_pointwise(conv) and conv.weight.dtype == torch.bfloat16
+            and binding.pw_gap_route(conv.in_channels, conv.out_channels, h * w, n)):
+        scale, bias = bn.folded_scale_bias()
+        return binding.pw_conv_gap_fwd(x, conv.weight, scale, bias, _ACT[bn.act])
+    y = conv_bn_eval(conv, bn, x)
+    return binding.gap_fwd(y.contiguous(memory_format=torch.channels_last))
+
+
 def _dw_w_t_cached(conv) -> torch.Tensor:
     """``binding._depthwise_w_t(conv.weight)`` ([9][C], tap-major), cached on
     the module until the weight mutates or moves (as ``_stem3_packed``)."""
