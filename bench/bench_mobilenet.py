@@ -82,6 +82,13 @@ The fused tail (``--only-tail-gap``, ``tail_gap*`` rows): the 320 -> 1280 conv
 step from a uint8 batch with the switch unset / ``0`` / ``1``. Same
 alternation, same rule (``binding.pw_gap_route`` holds the verdicts).
 
+The fused head (``--only-head-dense``, ``head_dense*`` rows): dropout + dense
+1280 -> 5 at batch 16 / 64 / 256 in training mode, ``DDLW_HEAD_DENSE=1``
+(``k_head_dense_fwd`` / ``_bwd``) vs ``=0`` (``k_dropout_fwd`` + ``nn.Linear``):
+forward only, and forward + ``softmax_ce_metrics`` + backward without and with
+dx; then the head step from a uint8 batch with the switch unset / ``0`` /
+``1``. Same alternation, same rule (``binding.head_dense_route``).
+
 Run on an MI355X:  python bench/bench_mobilenet.py [--batch 64]
 Prints one JSON line per layer shape, a table, and one final JSON line.
 """
@@ -931,6 +938,79 @@ def bench_tail_gap_end_to_end(B, dev, iters, rounds):
     return out
 
 
+# The rows of --only-head-dense: dropout + dense 1280 -> 5 of the transfer
+# head at these batches.
+HEAD_DENSE_BATCHES = [16, 64, 256]
+
+
+def bench_head_dense_stage(B, dev, iters, rounds, C=1280, K=5, p=0.5):
+    """The head stage as ``TransferModel.forward`` runs it, in training mode:
+    ``DDLW_HEAD_DENSE=0`` ("off": ``k_dropout_fwd`` + ``nn.Linear``) against
+    ``=1`` ("fused": ``k_head_dense_fwd`` / ``_bwd``), alternating. Three rows:
+    forward only; forward + ``softmax_ce_metrics`` + backward without dx (a
+    frozen base) and with dx (a trainable suffix)."""
+    from ddlw_amd.ops.layers import (Dropout, dropout_linear, dropout_linear_route,
+                                     softmax_ce_metrics)
+
+    torch.manual_seed(0)
+    drop = Dropout(p).train()
+    lin = torch.nn.Linear(C, K).to(dev).to(torch.bfloat16)
+    x = torch.randn(B, C, device=dev).to(torch.bfloat16)
+    xg = x.clone().requires_grad_(True)
+    labels = torch.randint(0, K, (B,), device=dev)
+
+    def head(xx):
+        if dropout_linear_route(xx, drop, lin):
+            return dropout_linear(xx, drop, lin)
+        return lin(drop(xx))
+
+    def fwd():
+        with torch.no_grad():
+            return head(x)
+
+    def fwd_bwd(xx):
+        def run():
+            lin.zero_grad(set_to_none=True)
+            xx.grad = None
+            loss, _ = softmax_ce_metrics(head(xx), labels)
+            loss.backward()
+            return loss
+        return run
+
+    recs = []
+    for what, fn in (("fwd", fwd), ("fwd_bwd", fwd_bwd(x)), ("fwd_bwd_dx", fwd_bwd(xg))):
+        fns = {"off": _with_env("DDLW_HEAD_DENSE", "0", fn),
+               "fused": _with_env("DDLW_HEAD_DENSE", "1", fn)}
+        rec = _deep_verdict(time_interleaved(fns, iters, rounds), "off")
+        recs.append({"kind": "head_dense", "what": what,
+                     "shape": f"n{B}_c{C}_k{K}", "N": B, **rec})
+    return recs
+
+
+def bench_head_dense_end_to_end(B, dev, iters, rounds):
+    """The head-training step of ``build_model(224, 224, 3, 5)`` from a uint8
+    batch with ``DDLW_HEAD_DENSE`` unset ("default": the measured table), ``0``
+    ("off") and ``1`` ("forced"), alternating in one process."""
+    torch.manual_seed(0)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device=dev)
+    x = u8.permute(0, 3, 1, 2)
+    labels = torch.randint(0, 5, (B,), device=dev)
+    os.environ.pop("DDLW_HEAD_DENSE", None)
+    model = apply_bf16_policy(build_model(224, 224, 3, 5).to(dev)).train()
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = softmax_cross_entropy(model(x), labels)
+        loss.backward()
+        opt.step()
+        return loss
+
+    s = time_interleaved({"default": step, "off": _with_env("DDLW_HEAD_DENSE", "0", step),
+                          "forced": _with_env("DDLW_HEAD_DENSE", "1", step)}, iters, rounds)
+    return {"head_dense_head_step_u8": _deep_verdict(s, "off")}
+
+
 def _stats(samples: dict, B=None) -> dict:
     out = {}
     for k, v in samples.items():
@@ -1058,6 +1138,8 @@ def main():
                     help="run only the one-kernel inverted residual rows and steps")
     ap.add_argument("--only-tail-gap", action="store_true",
                     help="run only the fused tail conv + GAP rows and steps")
+    ap.add_argument("--only-head-dense", action="store_true",
+                    help="run only the fused dropout + dense head rows and step")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -1066,9 +1148,19 @@ def main():
     dev = torch.device("cuda:0")
     B = args.batch
     if (args.only_stem_u8_train or args.only_dw_train or args.only_pw_deep
-            or args.only_mbconv_fused or args.only_tail_gap):
+            or args.only_mbconv_fused or args.only_tail_gap or args.only_head_dense):
         args.skip_layers = args.skip_e2e = args.skip_facade = True
     pw_deep = {}
+    if args.only_head_dense:
+        # the stage is tens of microseconds: ten times the calls per round
+        rows = [rec for b in HEAD_DENSE_BATCHES
+                for rec in bench_head_dense_stage(b, dev, args.iters * 10, args.rounds)]
+        for rec in rows:
+            print(json.dumps(rec), flush=True)
+        pw_deep = {"head_dense_stage": rows,
+                   **bench_head_dense_end_to_end(B, dev, args.e2e_iters, args.rounds)}
+        print(json.dumps({k: v for k, v in pw_deep.items() if k != "head_dense_stage"}),
+              flush=True)
     if args.only_tail_gap:
         # the pair is tens of microseconds: ten times the calls per round
         rows = [bench_tail_gap_layer(b, dev, args.iters * 10, args.rounds)

@@ -43,7 +43,8 @@ import torch.nn as nn
 
 from ..core.model_io import tag_model
 from ..ops.conv import Conv2d
-from ..ops.layers import BatchNormAct2d, GlobalAvgPool2d
+from ..ops.layers import (BatchNormAct2d, GlobalAvgPool2d, dropout_linear,
+                          dropout_linear_route)
 from ..ops import mbconv
 
 
@@ -319,6 +320,9 @@ class TransferModel(nn.Module):
             # the stock pool: the base pools, and a frozen one may fuse its
             # tail conv with the pool (ops/mbconv.py, ``conv_bn_gap_eval``)
             x = self.base(x, pooled=True)
+            if dropout_linear_route(x, self.dropout, self.classifier):
+                # dropout + dense in one kernel each way (hip/head_dense.hip)
+                return dropout_linear(x, self.dropout, self.classifier)
         else:
             x = self.global_average_pooling(self.base(x))  # fused GAP -> (N, C)
         x = self.dropout(x)

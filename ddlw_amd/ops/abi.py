@@ -71,6 +71,9 @@ SIGNATURES = {
     "ddlw_ce_metrics_nblocks": (_I, [_I, _I, _P]),
     "ddlw_ce_metrics": (_I, [_P] * 6 + [_I, _I, _F, _I, _P]),
     "ddlw_normalize_u8": (_I, [_P, _P, _L, _P]),
+    # head_dense.hip
+    "ddlw_head_dense_fwd": (_I, [_P] * 4 + [_L, _I, _I, _F, c_ulonglong, _P]),
+    "ddlw_head_dense_bwd": (_I, [_P] * 6 + [_L, _I, _I, _F, c_ulonglong, _I, _P]),
     # optim.hip
     "ddlw_fused_sgd": (_I, [_P, _I, _L, _F, _F, _F, _I, _P]),
     "ddlw_fused_adam": (_I, [_P, _I, _L, _F, _F, _F, _F, _F, _F, _F, _P]),

@@ -1263,6 +1263,91 @@ def dropout_bwd(dy: torch.Tensor, mask: torch.Tensor, p: float):
     return dx
 
 
+# ---- classifier head: dropout + dense in one launch each way ---------------- #
+
+_HEAD_DENSE_MAX_K = 64
+
+
+def head_dense_supported(C: int, K: int) -> bool:
+    """Shapes the ``head_dense`` kernels take: 16-byte bf16x8 vectors along
+    the features and at most four 16-class MFMA fragments."""
+    return C >= 8 and C % 8 == 0 and 1 <= K <= _HEAD_DENSE_MAX_K
+
+
+# (C, K) -> (smallest, largest) measured batch N of the --only-head-dense
+# table (bench/bench_mobilenet.py) at which the fused stage beat dropout +
+# nn.Linear by more than that stage's spread in both of two runs (rule and
+# figures: docs/KERNELS.md, "head_dense.hip").
+_HEAD_DENSE_MEASURED = {
+    # MobileNetV2 head: fwd 2.1x, fwd+bwd 1.05-1.47x, with dx 1.47-1.80x. At
+    # batch 256 the with-dx row was inside a 0.09 ms spread in one run: off.
+    (1280, 5): (16, 64),
+}
+
+
+def head_dense_route(C: int, K: int, N: int) -> bool:
+    """True: dropout + dense C -> K over ``N`` rows of pooled features runs
+    on the ``head_dense`` kernels (``hip/head_dense.hip``); False: on
+    ``dropout_fwd`` and ``nn.Linear``. ``DDLW_HEAD_DENSE``, read per call:
+    ``0`` -> never; ``1`` -> every supported shape; unset -> the measured
+    winners only, each within its measured batch range."""
+    if N < 1 or not head_dense_supported(C, K):
+        return False
+    return _route_mode("DDLW_HEAD_DENSE", _HEAD_DENSE_MEASURED, (C, K), N)
+
+
+def _head_dense_args(who, x, w, p):
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError(f"{who}: x is {tuple(x.shape)}, w is {tuple(w.shape)}; "
+                         f"want [N,C] and [K,C]")
+    (n, c), k = x.shape, w.shape[0]
+    if n < 1 or not head_dense_supported(c, k):
+        raise ValueError(f"{who}: N={n}, C={c}, K={k}: need N >= 1, C a multiple "
+                         f"of 8 and 1 <= K <= {_HEAD_DENSE_MAX_K}")
+    for name, t in (("x", x), ("w", w)):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous bf16, got {t.dtype}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{who}: p must be in [0, 1), got {p}")
+    return n, c, k
+
+
+def head_dense_fwd(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor],
+                   p: float, seed: int) -> torch.Tensor:
+    """``dropout_fwd(x, p, seed)[0] @ w.T + b`` in one launch, without the
+    dropped activations or a mask: x bf16 [N,C], w bf16 [K,C], b bf16 [K] or
+    None; fp32 accumulation, one rounding. ``p == 0`` is the plain dense
+    layer. Returns bf16 [N,K]."""
+    who = "head_dense_fwd"
+    n, c, k = _head_dense_args(who, x, w, p)
+    if b is not None and (b.dtype != torch.bfloat16 or tuple(b.shape) != (k,)
+                          or not b.is_contiguous()):
+        raise ValueError(f"{who}: b must be contiguous bf16 [{k}]")
+    y = torch.empty((n, k), dtype=torch.bfloat16, device=x.device)
+    launch("head_dense_fwd", x, w, b, y, n, c, k, float(p), seed & (2**64 - 1))
+    return y
+
+
+def head_dense_bwd(dlogits: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
+                   p: float, seed: int, want_dx: bool, want_db: bool):
+    """Backward of ``head_dense_fwd`` from ``dlogits`` [N,K] (bf16, or fp32
+    rounded to bf16 once as it is loaded) and the forward's ``(x, w, p,
+    seed)``: returns ``(dW [K,C], db [K] or None, dx [N,C] or None)``, bf16.
+    The dropped activations are regenerated, not read."""
+    who = "head_dense_bwd"
+    n, c, k = _head_dense_args(who, x, w, p)
+    if (tuple(dlogits.shape) != (n, k) or not dlogits.is_contiguous()
+            or dlogits.dtype not in (torch.bfloat16, torch.float32)):
+        raise ValueError(f"{who}: dlogits must be contiguous bf16 or fp32 {(n, k)}, "
+                         f"got {dlogits.dtype} {tuple(dlogits.shape)}")
+    dw = torch.empty_like(w)
+    db = torch.empty(k, dtype=torch.bfloat16, device=x.device) if want_db else None
+    dx = torch.empty_like(x) if want_dx else None
+    launch("head_dense_bwd", dlogits, x, w, dw, db, dx, n, c, k, float(p),
+           seed & (2**64 - 1), 1 if dlogits.dtype == torch.float32 else 0)
+    return dw, db, dx
+
+
 def argmax_rows(logits: torch.Tensor) -> torch.Tensor:
     """K12: per-row argmax (first-max tie-break, like torch.argmax)."""
     lf = logits.float().contiguous()

@@ -83,6 +83,18 @@ __device__ __forceinline__ int clamp_tap(int v, int hi) {
   return v < 0 ? 0 : (v > hi ? hi : v);
 }
 
+// The counter-based RNG of the dropout mask (k_dropout_fwd in head.hip and the
+// kernels of head_dense.hip that regenerate it): a 64-bit finalizer of
+// seed + flat element index, low 32 bits.
+__device__ __forceinline__ unsigned ddlw_hash32(unsigned long long s) {
+  s ^= s >> 33;
+  s *= 0xff51afd7ed558ccdULL;
+  s ^= s >> 33;
+  s *= 0xc4ceb9fe1a85ec53ULL;
+  s ^= s >> 33;
+  return (unsigned)s;
+}
+
 // launch geometry -----------------------------------------------------------
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 

@@ -57,17 +57,9 @@ DDLW_EXPORT int ddlw_softmax_ce(const void* logits, const void* labels,
 // K7: Dropout fwd/bwd (head path, B x 1280 — reference P1/02:174, p tunable
 // P2/01:197). Counter-based RNG (splitmix64 of (seed, index)): stateless,
 // deterministic given the seed, no curand dependency. Bitmask layout = one
-// byte per 8 elements (same convention as the BN ReLU mask).
+// byte per 8 elements (same convention as the BN ReLU mask). ddlw_hash32 is
+// in common.h: head_dense.hip regenerates this mask from it.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned ddlw_hash32(unsigned long long s) {
-  s ^= s >> 33;
-  s *= 0xff51afd7ed558ccdULL;
-  s ^= s >> 33;
-  s *= 0xc4ceb9fe1a85ec53ULL;
-  s ^= s >> 33;
-  return (unsigned)s;
-}
-
 __global__ __launch_bounds__(256) void k_dropout_fwd(
     const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
     unsigned char* __restrict__ mask, long n8, float p, float scale,

@@ -220,18 +220,78 @@ class Dropout(nn.Module):
         self._calls = 0
         self._base_seed = int(torch.initial_seed()) & (2**63 - 1)
 
+    def next_seed(self) -> int:
+        """The seed of the next mask; every kernel call that drops takes one
+        (``forward`` here, or the fused head of ``TransferModel``), so the mask
+        sequence does not depend on which of them runs."""
+        self._calls += 1
+        return self._base_seed + self._calls * 0x9E3779B97F4A7C15
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not self.training or self.p <= 0.0:
             return x
         if (x.is_cuda and x.dtype == torch.bfloat16 and x.numel() % 8 == 0
                 and not _hip_ops_disabled()):
-            self._calls += 1
-            seed = self._base_seed + self._calls * 0x9E3779B97F4A7C15
-            return _DropoutFn.apply(x, self.p, seed)
+            return _DropoutFn.apply(x, self.p, self.next_seed())
         return F.dropout(x, self.p, self.training)
 
     def extra_repr(self) -> str:
         return f"p={self.p}"
+
+
+# --------------------------------------------------------------------------- #
+# Dropout + dense in one kernel each way (hip/head_dense.hip)
+# --------------------------------------------------------------------------- #
+
+
+class _DropoutLinearFn(torch.autograd.Function):
+    """``linear(dropout(x, p, seed), w, b)`` on ``k_head_dense_fwd`` /
+    ``k_head_dense_bwd``. Saves x, w and the seed: no mask and no dropped
+    activations, the backward regenerates them. ``p == 0``: plain dense."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, p: float, seed: int):
+        x, w = x.contiguous(), w.contiguous()
+        ctx.save_for_backward(x, w)
+        ctx.p, ctx.seed, ctx.has_bias = p, seed, b is not None
+        return binding.head_dense_fwd(x, w, None if b is None else b.contiguous(),
+                                      p, seed)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, w = ctx.saved_tensors
+        if dlogits.dtype not in (torch.bfloat16, torch.float32):
+            dlogits = dlogits.float()
+        dw, db, dx = binding.head_dense_bwd(
+            dlogits.contiguous(), x, w, ctx.p, ctx.seed,
+            want_dx=ctx.needs_input_grad[0],
+            want_db=ctx.has_bias and ctx.needs_input_grad[2])
+        return dx, (dw if ctx.needs_input_grad[1] else None), db, None, None
+
+
+def dropout_linear_route(x: torch.Tensor, dropout: nn.Module, linear: nn.Module) -> bool:
+    """True when ``linear(dropout(x))`` takes ``_DropoutLinearFn``: CUDA bf16
+    [N, C] features, the stock ``Dropout`` with p < 1, an ``nn.Linear`` with
+    bf16 weight and bf16 or no bias, the HIP ops on, and
+    ``binding.head_dense_route`` (``DDLW_HEAD_DENSE``) saying yes."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2) or _hip_ops_disabled():
+        return False
+    if type(dropout) is not Dropout or not dropout.p < 1.0 or type(linear) is not nn.Linear:
+        return False
+    w, b = linear.weight, linear.bias
+    if w.dtype != torch.bfloat16 or (b is not None and b.dtype != torch.bfloat16):
+        return False
+    return binding.head_dense_route(x.shape[1], w.shape[0], x.shape[0])
+
+
+def dropout_linear(x: torch.Tensor, dropout: "Dropout", linear: nn.Linear) -> torch.Tensor:
+    """``linear(dropout(x))`` in one launch (``dropout_linear_route`` holds).
+    Training with p > 0 takes the next seed of ``dropout``, as its own forward
+    would; eval or p = 0 runs the plain-dense variant."""
+    drop = dropout.training and dropout.p > 0.0
+    return _DropoutLinearFn.apply(x, linear.weight, linear.bias,
+                                  dropout.p if drop else 0.0,
+                                  dropout.next_seed() if drop else 0)
 
 
 # --------------------------------------------------------------------------- #
