@@ -1011,6 +1011,82 @@ def bench_head_dense_end_to_end(B, dev, iters, rounds):
     return {"head_dense_head_step_u8": _deep_verdict(s, "off")}
 
 
+# The rows of --only-frozen-bn: the distinct stages of features[13:] @224 as
+# pointwise (H, C, K, act) and depthwise (H, C, stride).
+FROZEN_BN_PW = [(14, 96, 576, 2), (14, 576, 96, 0), (7, 576, 160, 0), (7, 160, 960, 2),
+                (7, 960, 160, 0), (7, 960, 320, 0), (7, 320, 1280, 2)]
+FROZEN_BN_DW = [(14, 576, 1), (14, 576, 2), (7, 960, 1)]
+
+
+def bench_frozen_bn_stage(B, H, C, K, act, stride, dev, iters, rounds):
+    """The backward of one conv + frozen-BN stage, per direction: the module
+    path it replaces ("module": ``_BnActFn`` in eval mode, then the conv
+    Function's backward) against the stage Function on the gated kernels
+    ("gated", ``DDLW_FROZEN_BN=1``), alternating. Each contender is
+    ``autograd.grad`` over a graph built once, with only the timed
+    direction's input wanting a gradient (a depthwise stage: both)."""
+    from ddlw_amd.ops import mbconv
+
+    torch.manual_seed(0)
+    dw = stride > 0
+    conv = (Conv2d(C, C, 3, stride=stride, padding=1, groups=C, bias=False) if dw
+            else Conv2d(C, K, 1, bias=False)).to(dev).to(torch.bfloat16).eval()
+    conv.pw_train = not dw
+    bn = _bn(K, act, dev)
+    for p in bn.parameters():
+        p.requires_grad = False
+    x = _cl(torch.randn(B, C, H, H, device=dev).to(torch.bfloat16))
+    recs = []
+    for what in (("bwd",) if dw else ("dgrad", "wgrad")):
+        x.requires_grad_(what != "wgrad")
+        conv.weight.requires_grad_(what != "dgrad")
+        wanted = [t for t in (x, conv.weight) if t.requires_grad]
+        y_mod = bn(conv(x))
+        y_new = mbconv.conv_bn_frozen(conv, bn, x)
+        dout = _cl(torch.randn_like(y_mod) / y_mod.numel() * K)
+        fns = {"module": lambda: torch.autograd.grad(y_mod, wanted, dout, retain_graph=True),
+               "gated": _with_env("DDLW_FROZEN_BN", "1", lambda: torch.autograd.grad(
+                   y_new, wanted, dout, retain_graph=True))}
+        rec = _deep_verdict(time_interleaved(fns, iters, rounds), "module")
+        M = B * y_mod.shape[2] * y_mod.shape[3]
+        kind = "dw_bwd" if dw else "pw_" + what
+        recs.append({"kind": "frozen_bn", "what": kind, "C": C, "K": K,
+                     "stride": max(stride, 1), "M": M,
+                     "shape": f"{H}x{H}_c{C}_k{K}_s{max(stride, 1)}", **rec})
+    return recs
+
+
+def bench_frozen_bn_step(B, dev, iters, rounds, k=13):
+    """The ``fine_tune_at=k`` training step under bf16 with
+    ``fine_tune_bn="frozen"`` and ``DDLW_FROZEN_BN`` unset ("default": the
+    measured table), ``1`` ("forced") and ``0`` ("off": the module path), and,
+    for orientation, the ``fine_tune_bn="batch"`` step, alternating in one
+    process."""
+    torch.manual_seed(0)
+    x = _cl(torch.randn(B, 3, 224, 224, device=dev).to(torch.bfloat16))
+    labels = torch.randint(0, 5, (B,), device=dev)
+    os.environ.pop("DDLW_FROZEN_BN", None)
+
+    def make(bn_mode):
+        model = apply_bf16_policy(build_model(
+            224, 224, 3, 5, fine_tune_at=k, fine_tune_bn=bn_mode).to(dev)).train()
+        opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4)
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            loss = softmax_cross_entropy(model(x), labels)
+            loss.backward()
+            opt.step()
+            return loss
+        return step
+
+    frozen, batch = make("frozen"), make("batch")
+    s = time_interleaved({"default": frozen, "off": _with_env("DDLW_FROZEN_BN", "0", frozen),
+                          "forced": _with_env("DDLW_FROZEN_BN", "1", frozen),
+                          "batch": batch}, iters, rounds)
+    return {f"frozen_bn_step_at_{k}": _deep_verdict(s, "off")}
+
+
 def _stats(samples: dict, B=None) -> dict:
     out = {}
     for k, v in samples.items():
@@ -1140,6 +1216,8 @@ def main():
                     help="run only the fused tail conv + GAP rows and steps")
     ap.add_argument("--only-head-dense", action="store_true",
                     help="run only the fused dropout + dense head rows and step")
+    ap.add_argument("--only-frozen-bn", action="store_true",
+                    help="run only the frozen-BN backward rows and fine-tuning steps")
     ap.add_argument("--fine-tune-at", type=int, nargs="*", default=[13, 3])
     ap.add_argument("--out", type=str, default="bench_out/mobilenet_report.json")
     args = ap.parse_args()
@@ -1148,9 +1226,21 @@ def main():
     dev = torch.device("cuda:0")
     B = args.batch
     if (args.only_stem_u8_train or args.only_dw_train or args.only_pw_deep
-            or args.only_mbconv_fused or args.only_tail_gap or args.only_head_dense):
+            or args.only_mbconv_fused or args.only_tail_gap or args.only_head_dense
+            or args.only_frozen_bn):
         args.skip_layers = args.skip_e2e = args.skip_facade = True
     pw_deep = {}
+    if args.only_frozen_bn:
+        rows = [rec for (H, C, K, act) in FROZEN_BN_PW
+                for rec in bench_frozen_bn_stage(B, H, C, K, act, 0, dev, args.iters, args.rounds)]
+        rows += [rec for (H, C, st) in FROZEN_BN_DW
+                 for rec in bench_frozen_bn_stage(B, H, C, C, 2, st, dev, args.iters, args.rounds)]
+        for rec in rows:
+            print(json.dumps(rec), flush=True)
+        pw_deep = {"frozen_bn_stages": rows,
+                   **bench_frozen_bn_step(B, dev, args.e2e_iters, args.rounds)}
+        print(json.dumps({k: v for k, v in pw_deep.items() if k != "frozen_bn_stages"}),
+              flush=True)
     if args.only_head_dense:
         # the stage is tens of microseconds: ten times the calls per round
         rows = [rec for b in HEAD_DENSE_BATCHES
@@ -1301,7 +1391,7 @@ def main():
     summary.update(facade)
     summary.update({k: v for k, v in pw_deep.items()
                     if k not in ("pw_deep_layers", "mbconv_fused_blocks",
-                                 "tail_gap_layers")})
+                                 "tail_gap_layers", "frozen_bn_stages")})
     print(json.dumps(summary), flush=True)
 
 

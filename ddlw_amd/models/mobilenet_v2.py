@@ -17,6 +17,8 @@ learning rate). The trainable suffix follows ``train()``/``eval()`` like any
 module, so its BatchNorms use *batch* statistics in training. That is what
 the reference's per-layer ``trainable`` flags give; it is NOT the Keras
 fine-tuning recipe that keeps calling the base with ``training=False``.
+``fine_tune_bn="frozen"`` selects that recipe, with frozen BatchNorms
+(``FrozenBase``).
 
 Activations: every BN + ReLU6 pair is one fused ``BatchNormAct2d(act=
 "relu6")``; an ``nn.Identity`` keeps the old ReLU6 slot so ``state_dict``
@@ -88,6 +90,10 @@ class InvertedResidual(nn.Module):
             # trainable block: pointwise conv + BN stages with the statistics
             # out of the conv epilogue (ops/mbconv.py)
             return mbconv.inverted_residual_train_forward(self, x)
+        if mbconv.inverted_residual_frozen_bn_fusable(self, x):
+            # trainable convs under frozen BNs (``fine_tune_bn="frozen"``):
+            # folded forward kernels, gated backward kernels (ops/mbconv.py)
+            return mbconv.inverted_residual_frozen_bn_forward(self, x)
         return x + self.conv(x) if self.use_res else self.conv(x)
 
 
@@ -207,20 +213,45 @@ class FrozenBase(nn.Module):
     ``base.features[:k]`` keeps ``requires_grad=False``, stays in ``eval()``
     and runs under ``no_grad``. ``None`` (default) or ``len(features)``
     freezes everything, with the whole base in one ``no_grad`` forward.
+
+    ``fine_tune_bn`` says what the BatchNorms of the trainable suffix do.
+    ``"batch"`` (default): they train on batch statistics, as above.
+    ``"frozen"``: the Keras fine-tuning recipe's ``training=False`` base in
+    the ``FrozenBatchNorm2d`` convention. Every BN of the base stays in eval
+    mode, its ``weight`` / ``bias`` get ``requires_grad=False``, its running
+    buffers and ``num_batches_tracked`` are never touched, and only the conv
+    weights of the suffix train. (Keras would still train gamma / beta under
+    the moving statistics; here each BN is a constant per-channel affine.)
+    On CUDA bf16 such a block runs on the folded forward kernels and the
+    gated backward kernels (``ops/mbconv.py``, ``DDLW_FROZEN_BN``).
     """
 
     accepts_uint8 = True  # hands a uint8 batch to ``base.stem_entry``
+    FINE_TUNE_BN = ("batch", "frozen")
 
-    def __init__(self, base: nn.Module, fine_tune_at: Optional[int] = None):
+    def __init__(self, base: nn.Module, fine_tune_at: Optional[int] = None,
+                 fine_tune_bn: str = "batch"):
         super().__init__()
         self.base = base
-        self.set_fine_tune_at(fine_tune_at)
+        self._bn_mode = "batch"
+        self.set_fine_tune_at(fine_tune_at, fine_tune_bn)
 
     def _num_features(self) -> Optional[int]:
         feats = getattr(self.base, "features", None)
         return len(feats) if isinstance(feats, nn.Sequential) else None
 
-    def set_fine_tune_at(self, fine_tune_at: Optional[int]) -> None:
+    @property
+    def fine_tune_bn(self) -> str:
+        return self._bn_mode
+
+    def set_fine_tune_at(self, fine_tune_at: Optional[int],
+                         fine_tune_bn: Optional[str] = None) -> None:
+        """``fine_tune_bn=None`` keeps the current BN mode."""
+        if fine_tune_bn is not None:
+            if fine_tune_bn not in self.FINE_TUNE_BN:
+                raise ValueError(f"fine_tune_bn must be one of {self.FINE_TUNE_BN}, "
+                                 f"got {fine_tune_bn!r}")
+            self._bn_mode = fine_tune_bn
         n = self._num_features()
         if fine_tune_at is None:
             k = n
@@ -241,6 +272,11 @@ class FrozenBase(nn.Module):
             for i, m in enumerate(self.base.features):
                 for p in m.parameters():
                     p.requires_grad = i >= k
+            if self._bn_mode == "frozen":
+                for m in self.base.modules():
+                    if isinstance(m, (nn.BatchNorm2d, BatchNormAct2d)):
+                        m.weight.requires_grad = False
+                        m.bias.requires_grad = False
         self.train(self.training)
 
     @property
@@ -252,8 +288,9 @@ class FrozenBase(nn.Module):
 
     def train(self, mode: bool = True) -> "FrozenBase":
         super().train(mode)
-        if self._fully_frozen():
-            # stay frozen: never switch the base to train-mode BN
+        if self._fully_frozen() or self._bn_mode == "frozen":
+            # stay frozen: never switch the base to train-mode BN (nothing
+            # else in the base depends on the mode)
             self.base.eval()
         else:
             for m in self.base.features[: self._split]:
@@ -283,7 +320,18 @@ class FrozenBase(nn.Module):
         with torch.no_grad():
             for m in feats[start: self._split]:
                 x = m(x)
-        for m in feats[max(start, self._split):]:
+        first, n = max(start, self._split), len(feats)
+        if (self._bn_mode == "frozen" and isinstance(self.base, MobileNetV2)
+                and first <= n - 3):
+            # the 320 -> 1280 tail conv + BN + ReLU6 of a frozen-BN suffix is
+            # one pointwise stage (the blocks route themselves)
+            for m in feats[first: n - 3]:
+                x = m(x)
+            if mbconv.conv_bn_frozen_fusable(feats[n - 3], feats[n - 2], x):
+                x = mbconv.conv_bn_frozen(feats[n - 3], feats[n - 2], x)
+                return _POOL(x) if pooled else x
+            first = n - 3
+        for m in feats[first:]:
             x = m(x)
         return _POOL(x) if pooled else x
 
@@ -291,28 +339,34 @@ class FrozenBase(nn.Module):
 class TransferModel(nn.Module):
     """Frozen base -> GAP -> Dropout -> Dense(num_classes) logits
     (reference ``.../02_model_training_single_node.py:171-176``).
-    ``fine_tune_at``: see ``FrozenBase``."""
+    ``fine_tune_at``, ``fine_tune_bn``: see ``FrozenBase``."""
 
     accepts_uint8 = True  # the base takes the uint8 batch
 
     def __init__(self, channels: int = 3, num_classes: int = 5, dropout: float = 0.5,
-                 fine_tune_at: Optional[int] = None):
+                 fine_tune_at: Optional[int] = None, fine_tune_bn: str = "batch"):
         super().__init__()
-        self.base = FrozenBase(MobileNetV2(channels), fine_tune_at)
+        self.base = FrozenBase(MobileNetV2(channels), fine_tune_at, fine_tune_bn)
         self.global_average_pooling = GlobalAvgPool2d()
         from ..ops.layers import Dropout as DdlwDropout
 
         self.dropout = DdlwDropout(dropout)  # K7 kernel on GPU, stock on CPU
         self.classifier = nn.Linear(1280, num_classes)
 
-    def set_fine_tune_at(self, fine_tune_at: Optional[int]) -> None:
+    def set_fine_tune_at(self, fine_tune_at: Optional[int],
+                         fine_tune_bn: Optional[str] = None) -> None:
         """Switch the frozen/trainable split of the base in place (phase 2
-        after head training); a saved model keeps the new split. An
-        optimizer built earlier does not see newly trainable parameters."""
-        self.base.set_fine_tune_at(fine_tune_at)
+        after head training), and with ``fine_tune_bn`` the BN mode of the
+        suffix (``None`` keeps it); a saved model keeps both. An optimizer
+        built earlier does not see newly trainable parameters."""
+        self.base.set_fine_tune_at(fine_tune_at, fine_tune_bn)
         spec = getattr(self, "_ddlw_builder_spec", None)
         if spec is not None:
             spec[1]["fine_tune_at"] = fine_tune_at
+            # the key exists only for "frozen": a default spec stays as it was
+            spec[1].pop("fine_tune_bn", None)
+            if self.base.fine_tune_bn == "frozen":
+                spec[1]["fine_tune_bn"] = "frozen"
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if (type(self.global_average_pooling) is GlobalAvgPool2d
@@ -336,24 +390,27 @@ def build_model(
     num_classes: int = 5,
     dropout: float = 0.5,
     fine_tune_at: Optional[int] = None,
+    fine_tune_bn: str = "batch",
 ) -> TransferModel:
     """``fine_tune_at=k`` makes ``features[k:]`` of the MobileNetV2 base
     trainable (23 children: 0-2 stem, 3-19 inverted residuals, 20-22 the
-    1x1 tail); ``None`` or 23 keeps the whole base frozen. The trainable
-    part follows the reference's per-layer ``trainable`` flags: its
-    BatchNorms use batch statistics in training (not Keras's
-    ``training=False`` fine-tuning recipe)."""
+    1x1 tail); ``None`` or 23 keeps the whole base frozen. With
+    ``fine_tune_bn="batch"`` (default) the trainable part follows the
+    reference's per-layer ``trainable`` flags: its BatchNorms use batch
+    statistics in training. ``fine_tune_bn="frozen"`` is the Keras
+    ``training=False`` fine-tuning recipe with frozen BatchNorms: moving
+    statistics, constant gamma / beta, only the conv weights of the suffix
+    train (``FrozenBase``)."""
     m = TransferModel(channels=img_channels, num_classes=num_classes, dropout=dropout,
-                      fine_tune_at=fine_tune_at)
-    return tag_model(
-        m,
-        "mobilenet_v2_head",
-        dict(
-            img_height=img_height,
-            img_width=img_width,
-            img_channels=img_channels,
-            num_classes=num_classes,
-            dropout=dropout,
-            fine_tune_at=fine_tune_at,
-        ),
+                      fine_tune_at=fine_tune_at, fine_tune_bn=fine_tune_bn)
+    spec = dict(
+        img_height=img_height,
+        img_width=img_width,
+        img_channels=img_channels,
+        num_classes=num_classes,
+        dropout=dropout,
+        fine_tune_at=fine_tune_at,
     )
+    if fine_tune_bn == "frozen":  # only then: a default spec stays as it was
+        spec["fine_tune_bn"] = "frozen"
+    return tag_model(m, "mobilenet_v2_head", spec)

@@ -85,6 +85,7 @@ SIGNATURES = {
     "ddlw_depthwise_fwd_stats": (_I, [_P] * 5 + [_I] * 8 + [_P]),
     "ddlw_depthwise_bwd_bn_nparts": (_I, [_I, _I, _I, _P]),
     "ddlw_depthwise_bwd_bn": (_I, [_P] * 13 + [_I] * 5 + [_P]),
+    "ddlw_depthwise_bwd_gated": (_I, [_P] * 8 + [_I] * 8 + [_P]),
     "ddlw_depthwise_dgrad": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "ddlw_depthwise_wgrad_nparts": (_I, [_L, _I]),
     "ddlw_depthwise_wgrad": (_I, [_P, _P, _P, _P] + [_I] * 10 + [_P]),
@@ -96,6 +97,10 @@ SIGNATURES = {
     "ddlw_pw_conv_deep_fwd": (_I, [_P] * 6 + [_I, _L, _I, _I, _I, _P]),
     "ddlw_pw_conv_deep_nparts": (_I, [_L, _I, _P]),
     "ddlw_pw_conv_deep_fwd_stats": (_I, [_P] * 5 + [_L, _I, _I, _I, _P]),
+    # pointwise_frozen.hip
+    "ddlw_pw_dgrad_gated": (_I, [_P] * 6 + [_I, _L, _I, _I, _P]),
+    "ddlw_pw_wgrad_gated_nparts": (_I, [_L, _I, _I, _P]),
+    "ddlw_pw_wgrad_gated": (_I, [_P] * 6 + [_I, _L, _I, _I, _P]),
     # pointwise_gap.hip
     "ddlw_pw_conv_gap_fwd": (_I, [_P] * 5 + [_I] * 6 + [_P]),
     # mbconv_fused.hip

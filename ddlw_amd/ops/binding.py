@@ -1247,6 +1247,154 @@ def depthwise_bwd_bn(dout, mask, y, x, weight, mean, rstd, gamma, dbeta,
     return dx, dw
 
 
+# ---- conv + frozen BatchNorm, backward on the gated kernels ----------------- #
+#
+# One definition for all three (hip/pointwise_frozen.hip): with ``out`` the
+# bf16 tensor the folded forward kernel wrote,
+#   g16 = gate(out) ? bf16(fp32(dout) * scale[k]) : 0,
+#   gate = 1 for act 0 (none), 0 < out < 6 for act 2 (ReLU6),
+# formed in registers and never stored.
+
+
+def pw_gated_supported(C: int, K: int) -> bool:
+    """Shapes ``pw_dgrad_gated`` / ``pw_wgrad_gated`` take (conv C -> K)."""
+    return pw_conv_supported(C, K)
+
+
+def dw_gated_supported(C: int, kernel: int = 3, stride: int = 1,
+                       padding: int = 1) -> bool:
+    """Shapes ``depthwise_bwd_gated`` takes: 3x3, pad 1, stride 1 or 2."""
+    return C > 0 and C % 8 == 0 and kernel == 3 and padding == 1 and stride in (1, 2)
+
+
+# (kind, C, K, stride) -> (smallest, largest measured M): the rows of the
+# --only-frozen-bn table (bench/bench_mobilenet.py) that beat the path they
+# replace by more than its spread in both of two runs (docs/KERNELS.md,
+# "Conv + frozen BatchNorm, backward").
+_FROZEN_BN_MEASURED = {
+    # features[13:] @224, batch 64: every row won in both runs (the stages are
+    # launch-bound at these sizes: one or two launches against three to five)
+    ("pw_dgrad", 96, 576, 1): (12544, 12544),     # 2.5x, 1.5x
+    ("pw_wgrad", 96, 576, 1): (12544, 12544),     # 2.2x, 1.5x
+    ("pw_dgrad", 576, 96, 1): (12544, 12544),     # 2.1x, 1.5x
+    ("pw_wgrad", 576, 96, 1): (12544, 12544),     # 2.2x, 1.5x
+    ("pw_dgrad", 576, 160, 1): (3136, 3136),      # 2.0x, 1.5x
+    ("pw_wgrad", 576, 160, 1): (3136, 3136),      # 2.2x, 1.5x
+    ("pw_dgrad", 160, 960, 1): (3136, 3136),      # 1.6x, 1.5x
+    ("pw_wgrad", 160, 960, 1): (3136, 3136),      # 2.2x, 1.5x
+    ("pw_dgrad", 960, 160, 1): (3136, 3136),      # 2.1x, 1.4x
+    ("pw_wgrad", 960, 160, 1): (3136, 3136),      # 2.1x, 1.5x
+    ("pw_dgrad", 960, 320, 1): (3136, 3136),      # 2.0x, 1.5x
+    ("pw_wgrad", 960, 320, 1): (3136, 3136),      # 2.1x, 1.5x
+    ("pw_dgrad", 320, 1280, 1): (3136, 3136),     # 1.1x, 1.4x: the 1280-deep reduction
+    ("pw_wgrad", 320, 1280, 1): (3136, 3136),     # 2.1x, 1.5x
+    ("dw_bwd", 576, 576, 1): (12544, 12544),      # 1.4x, 1.5x
+    ("dw_bwd", 576, 576, 2): (3136, 3136),        # 1.6x, 1.5x
+    ("dw_bwd", 960, 960, 1): (3136, 3136),        # 1.9x, 1.5x
+}
+
+_FROZEN_BN_KINDS = ("pw_dgrad", "pw_wgrad", "dw_bwd")
+
+
+def frozen_bn_route(kind: str, C: int, K: int, stride: int, M: int) -> bool:
+    """True: this direction of a conv + frozen-BN stage (``"pw_dgrad"`` /
+    ``"pw_wgrad"`` of a 1x1 conv C -> K, ``"dw_bwd"`` of a depthwise 3x3 with
+    C == K channels) over M output rows runs on the gated kernel; False: on
+    the kernels it replaces (g16 formed elementwise, then the plain dgrad /
+    wgrad). ``DDLW_FROZEN_BN``, read per call: ``0`` -> never, ``1`` -> every
+    supported shape, unset -> the measured winners only."""
+    if kind not in _FROZEN_BN_KINDS:
+        raise ValueError(f"frozen_bn_route: unknown kind {kind!r}")
+    if kind == "dw_bwd":
+        if C != K or not dw_gated_supported(C, 3, stride, 1):
+            return False
+    elif stride != 1 or not pw_gated_supported(C, K):
+        return False
+    return M > 0 and _route_mode("DDLW_FROZEN_BN", _FROZEN_BN_MEASURED,
+                                 (kind, C, K, stride), M)
+
+
+def _gated_args(who, dout, out, scale, act, K):
+    if act not in (0, 2):
+        raise ValueError(f"{who}: act must be 0 (none) or 2 (ReLU6), got {act}")
+    assert out.shape == dout.shape, f"{who}: out and dout differ in shape"
+    return _nhwc(dout), (_nhwc(out) if act == 2 else None), _f32c(scale, K)
+
+
+def pw_dgrad_gated(dout: torch.Tensor, out: torch.Tensor, weight: torch.Tensor,
+                   scale: torch.Tensor, act: int, in_shape,
+                   acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of a 1x1 conv + frozen-BN stage: ``dx[m][c] =
+    bf16(sum_k g16[m][k] * w[k][c] (+ acc[m][c]))``. dout/out channels_last
+    bf16 [N,K,H,W] (or rows [M,K]); weight [K,C,1,1]; scale fp32 [K]; ``acc``
+    a dx-shaped bf16 tensor added before the one rounding (the gradient that
+    joins at the stage's input). The weight is transposed here per call, as
+    ``pw_conv_dgrad`` does (it changes every step)."""
+    w2 = _pw_w2(weight)
+    K, C = w2.shape
+    if not pw_gated_supported(C, K):
+        raise ValueError(f"pw_dgrad_gated: C={C}, K={K} must be multiples of 8")
+    rows, kd = _rows_c(dout)
+    assert kd == K, f"pw_dgrad_gated: dout has {kd} channels, weight {K}"
+    dout, out, scale = _gated_args("pw_dgrad_gated", dout, out, scale, act, K)
+    dx = _pw_out(dout, rows, C, None, "pw_dgrad_gated")
+    assert tuple(dx.shape) == tuple(in_shape), "pw_dgrad_gated: in_shape"
+    if acc is not None:
+        assert acc.shape == dx.shape, "pw_dgrad_gated: acc must match dx"
+        acc = _nhwc(acc)
+    launch("pw_dgrad_gated", dout, out, w2.t().contiguous(), scale, dx, acc,
+           int(act), rows, C, K)
+    return dx
+
+
+def pw_wgrad_gated(dout: torch.Tensor, out: torch.Tensor, x: torch.Tensor,
+                   scale: torch.Tensor, act: int, weight_shape) -> torch.Tensor:
+    """Weight gradient of a 1x1 conv + frozen-BN stage, bf16 of
+    ``weight_shape``: ``dw[k][c] = bf16(sum_m g16[m][k] * x[m][c])``. Row
+    slices into fp32 partials, then a fixed-order fold: bit-reproducible."""
+    K, C = int(weight_shape[0]), int(weight_shape[1])
+    if not pw_gated_supported(C, K):
+        raise ValueError(f"pw_wgrad_gated: C={C}, K={K} must be multiples of 8")
+    rows, kd = _rows_c(dout)
+    rx, cx = _rows_c(x)
+    assert (kd, cx, rx) == (K, C, rows), "pw_wgrad_gated: dout / x / weight_shape disagree"
+    dout, out, scale = _gated_args("pw_wgrad_gated", dout, out, scale, act, K)
+    dw = torch.empty(tuple(weight_shape), dtype=torch.bfloat16, device=x.device)
+    if rows == 0:
+        return dw.zero_()
+    nparts = int(query("pw_wgrad_gated_nparts", rows, C, K, None))
+    part = torch.empty(nparts, K, C, dtype=torch.float32, device=x.device)
+    launch("pw_wgrad_gated", dout, out, _nhwc(x), scale, part, dw, int(act),
+           rows, C, K)
+    return dw
+
+
+def depthwise_bwd_gated(dout: torch.Tensor, out: torch.Tensor, x: torch.Tensor,
+                        weight: torch.Tensor, scale: torch.Tensor, act: int,
+                        stride: int, need_dx: bool):
+    """Backward of a depthwise 3x3 pad-1 conv (stride 1 or 2) + frozen-BN
+    stage in one kernel: returns ``(dx | None, dw)``, dx channels_last bf16
+    like ``x`` (the transposed conv of g16 with the weight), dw fp32
+    ``[C,1,3,3]`` like ``depthwise_wgrad``. Bit-reproducible."""
+    n, c, h, w = x.shape
+    assert tuple(weight.shape) == (c, 1, 3, 3), "depthwise_bwd_gated: weight must be [C,1,3,3]"
+    if not dw_gated_supported(c, 3, stride, 1):
+        raise ValueError(f"depthwise_bwd_gated: C={c}, stride={stride} not supported")
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    assert tuple(dout.shape) == (n, c, ho, wo), \
+        f"depthwise_bwd_gated: dout is {tuple(dout.shape)}, the output is {(n, c, ho, wo)}"
+    dout, out, scale = _gated_args("depthwise_bwd_gated", dout, out, scale, act, c)
+    nparts = int(query("depthwise_bwd_bn_nparts", n, h, w, None))
+    part = torch.empty(nparts, 9, c, dtype=torch.float32, device=x.device)
+    dw = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
+    dx = (torch.empty((n, c, h, w), dtype=torch.bfloat16, device=x.device,
+                      memory_format=torch.channels_last) if need_dx else None)
+    launch("depthwise_bwd_gated", dout, out, _nhwc(x),
+           _depthwise_w_t(weight) if need_dx else None, scale, dx, part, dw,
+           n, h, w, c, ho, wo, stride, int(act))
+    return dx, dw
+
+
 def dropout_fwd(x: torch.Tensor, p: float, seed: int):
     """K7: bitmask dropout (counter-based RNG, deterministic per seed).
     Returns (y, mask); x flat-size must be a multiple of 8."""

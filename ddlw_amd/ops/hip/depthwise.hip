@@ -1,7 +1,8 @@
 // Depthwise conv2d (K2 — MobileNetV2's depthwise blocks), NHWC bf16, fp32
 // accumulation: training forward, eval forward with the folded-BN epilogue,
 // the 3x3 backward (dgrad, wgrad + finalize), and the training stage fused
-// with its BatchNorm (forward with statistics, stride-1 BN dx + dgrad + wgrad).
+// with its BatchNorm (forward with statistics, stride-1 BN dx + dgrad + wgrad),
+// and the backward of the stage under a FROZEN BatchNorm (stride 1 and 2).
 // Data conventions of the whole family: C % 8 == 0, 16-byte bf16x8 accesses,
 // weights pre-transposed host-side to [R*S][C] so the per-tap weight read is
 // the same contiguous vector shape as the activation read.
@@ -604,6 +605,180 @@ __global__ __launch_bounds__(256, 2) DW_NO_PK_F32 void k_depthwise_bwd_bn(
 }
 
 // ---------------------------------------------------------------------------
+// Pad-1 backward of depthwise conv + FROZEN BatchNorm (+ ReLU6), stride 1 or
+// 2, in one kernel. With constant statistics dz needs no reduction:
+//   g16 = gate(out) ? bf16(fp32(dout) * scale[c]) : 0,
+//   gate = 1 (ACT 0) | 0 < out < 6 on the saved bf16 output (ACT 2),
+// the definition of pointwise_frozen.hip, formed while staging.
+//
+// k_depthwise_bwd_bn's persistent design (8 x 8 pixels x DWB_CV vectors per
+// block, grid.y slices the (image, tile) list, g16 of the tile plus halo
+// double-buffered in LDS as bf16, wgrad accumulators in registers across
+// tiles, one [9][C] partial per block for k_depthwise_wgrad_finalize), with
+// the tile laid over the INPUT pixels, which is what lets stride 2 in: input
+// pixel (h, w) meets output pixel ((h+1-r)/S, (w+1-s)/S) through tap (r, s)
+// when both divisions are exact, and that one g16 vector serves both
+//   dx[h][w]  += g16 * w[r][s]     and     dW[r][s] += g16 * x[h][w].
+// So a thread loads its own x vector once (no tap loads from global, clamped
+// or otherwise), reads nine g16 vectors from LDS and feeds both sums. The
+// staged g16 tile is 10 x 10 output pixels from (h0-1, w0-1) at stride 1 and
+// 5 x 5 from (h0/2, w0/2) at stride 2 (h0, w0 multiples of 8); positions
+// outside the output are ZERO, and at stride 2 a tap of the wrong parity
+// reads an in-range slot and is masked. No atomics, fixed order.
+// ---------------------------------------------------------------------------
+template <int STRIDE, int ACT, bool DX>
+__global__ __launch_bounds__(256, 2) DW_NO_PK_F32 void k_depthwise_bwd_gated(
+    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ out,
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ w_t,
+    const float* __restrict__ scale, bf16_t* __restrict__ dx,
+    float* __restrict__ part, int N, int H, int W_, int C, int Ho, int Wo) {
+  static_assert(DWB_TH * DWB_TW * DWB_CV == 256, "one thread per (pixel, vector)");
+  static_assert(DWB_TH == 8 && DWB_TW == 8, "tile origins must be even");
+  constexpr int GW = STRIDE == 1 ? DWB_TW + 2 : DWB_TW / 2 + 1;   // staged width
+  constexpr int GH = STRIDE == 1 ? DWB_TH + 2 : DWB_TH / 2 + 1;
+  const int vecC = C >> 3;
+  const int tid = threadIdx.x;
+  const int lv = tid % DWB_CV;                   // vector within the group
+  const int lp = tid / DWB_CV;                   // pixel within the tile
+  const int vec = blockIdx.x * DWB_CV + lv;
+  const bool vok = vec < vecC;
+  const long coff = (long)vec * 8;
+
+  float sc[8];
+  bf16x8 vw[DW_K * DW_K];
+  if (vok) {
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) sc[k] = scale[vec * 8 + k];
+    if (DX) {
+      #pragma unroll
+      for (int t = 0; t < DW_K * DW_K; ++t)
+        vw[t].v = *reinterpret_cast<const uint4*>(w_t + (long)t * C + coff);
+    }
+  }
+
+  float acc[DW_K * DW_K][8];
+  #pragma unroll
+  for (int t = 0; t < DW_K * DW_K; ++t)
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) acc[t][k] = 0.f;
+
+  __shared__ uint4 sg[2][GH * GW * DWB_CV];
+  const int tiles_w = (W_ + DWB_TW - 1) / DWB_TW;
+  const int tiles_h = (H + DWB_TH - 1) / DWB_TH;
+  const int ntiles = N * tiles_h * tiles_w;
+  const int py = lp / DWB_TW, px = lp % DWB_TW;
+  int buf = 0;
+  #pragma unroll 1
+  for (int tile = (int)blockIdx.y; tile < ntiles; tile += (int)gridDim.y, buf ^= 1) {
+    const unsigned tw = (unsigned)tile % (unsigned)tiles_w;
+    const unsigned tt = (unsigned)tile / (unsigned)tiles_w;
+    const int th = (int)(tt % (unsigned)tiles_h);
+    const int n = (int)(tt / (unsigned)tiles_h);
+    const int h0 = th * DWB_TH, w0 = (int)tw * DWB_TW;
+    const int gh0 = STRIDE == 1 ? h0 - 1 : h0 / 2;
+    const int gw0 = STRIDE == 1 ? w0 - 1 : w0 / 2;
+
+    // 1. g16 of the staged output pixels -> LDS (item = pixel * DWB_CV + lv)
+    #pragma unroll 1
+    for (int it = tid; it < GH * GW * DWB_CV; it += 256) {
+      const int gp = it / DWB_CV;
+      const int ho = gh0 + gp / GW, wo = gw0 + gp % GW;
+      bf16x8 o;
+      dw_zero(o);
+      if (vok && ho >= 0 && ho < Ho && wo >= 0 && wo < Wo) {
+        const int pix = (n * Ho + ho) * Wo + wo;
+        bf16x8 vg, vy;
+        vg.v = *reinterpret_cast<const uint4*>(dout + (long)pix * C + coff);
+        if (ACT == 2) vy.v = *reinterpret_cast<const uint4*>(out + (long)pix * C + coff);
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          o.h[k] = f2b(b2f(vg.h[k]) * sc[k]);
+          if (ACT == 2) {
+            const float ov = b2f(vy.h[k]);
+            if (!(ov > 0.f && ov < 6.f)) o.h[k] = 0;
+          }
+        }
+      }
+      sg[buf][it] = o.v;
+    }
+    dw_barrier();
+
+    const int h = h0 + py, w = w0 + px;
+    if (vok && h < H && w < W_) {
+      bf16x8 own;
+      own.v = *reinterpret_cast<const uint4*>(x + (long)((n * H + h) * W_ + w) * C + coff);
+      float xf[8], a[8];
+      #pragma unroll
+      for (int k = 0; k < 8; ++k) { xf[k] = b2f(own.h[k]); a[k] = 0.f; }
+      // 2. tap (r, s): output pixel ((h+1-r)/S, (w+1-s)/S). In tile terms
+      // q = py + 1 - r in [-1, 8]: slot q + 1 at stride 1; at stride 2 slot
+      // q / 2 when q is even, and (q + 1) >> 1 is that slot for an even q
+      // and an in-range one (masked) for an odd q.
+      #pragma unroll
+      for (int r = 0; r < DW_K; ++r) {
+        const int qy = py + 1 - r;
+        const int ly = STRIDE == 1 ? qy + 1 : (qy + 1) >> 1;
+        const bool oky = STRIDE == 1 || !(qy & 1);
+        #pragma unroll
+        for (int s = 0; s < DW_K; ++s) {
+          const int qx = px + 1 - s;
+          const int lx = STRIDE == 1 ? qx + 1 : (qx + 1) >> 1;
+          const bool ok = oky && (STRIDE == 1 || !(qx & 1));
+          bf16x8 vd;
+          vd.v = sg[buf][(ly * GW + lx) * DWB_CV + lv];
+          if (STRIDE != 1) dw_keep_if(vd, ok);
+          float g[8];
+          #pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            g[k] = b2f(vd.h[k]);
+            acc[r * DW_K + s][k] += g[k] * xf[k];
+          }
+          if (DX) {
+            keep_packed(vw[r * DW_K + s].v);
+            #pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] += g[k] * b2f(vw[r * DW_K + s].h[k]);
+          }
+        }
+      }
+      if (DX) {
+        bf16x8 o;
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) o.h[k] = f2b(a[k]);
+        *reinterpret_cast<uint4*>(dx + (long)((n * H + h) * W_ + w) * C + coff) = o.v;
+      }
+    }
+  }
+
+  // fold the accumulators over the block's 64 pixels, one tap at a time, as
+  // k_depthwise_bwd_bn does: thread (grp, out) sums pixels grp*8 .. grp*8+7
+  // of output out = (lv, k) in order, then the first 32 threads add the 8
+  // group sums in order
+  __shared__ float red[256 * 8];
+  __shared__ float red2[8][DWB_CV * 8];
+  const int outi = tid % (DWB_CV * 8), grp = tid / (DWB_CV * 8);
+  const int ov = outi >> 3, ok8 = outi & 7;
+  const int ovec = blockIdx.x * DWB_CV + ov;
+  float* pout = part + (long)blockIdx.y * (DW_K * DW_K) * C + (long)ovec * 8 + ok8;
+  #pragma unroll
+  for (int t = 0; t < DW_K * DW_K; ++t) {
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) red[tid * 8 + k] = acc[t][k];
+    dw_barrier();
+    float a = 0.f;
+    #pragma unroll
+    for (int i = 0; i < 8; ++i) a += red[((grp * 8 + i) * DWB_CV + ov) * 8 + ok8];
+    red2[grp][outi] = a;
+    dw_barrier();                            // also frees red for the next tap
+    if (grp == 0 && ovec < vecC) {
+      a = red2[0][outi];
+      #pragma unroll
+      for (int i = 1; i < 8; ++i) a += red2[i][outi];
+      pout[(long)t * C] = a;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host entry points
 // ---------------------------------------------------------------------------
 static int dw_check(const char* who, int C, int R, int S, int stride, int pad,
@@ -727,6 +902,48 @@ DDLW_EXPORT int ddlw_depthwise_bwd_bn(const void* dout, const void* mask,
           (bf16_t*)dx, (float*)part, N, H, W_, C);
     });
   });
+  hipLaunchKernelGGL(k_depthwise_wgrad_finalize,
+                     dim3((C + 31) / 32, DW_K * DW_K), dim3(256), 0,
+                     (hipStream_t)stream, (const float*)part, (float*)dw, C,
+                     nparts);
+  DDLW_CHECK_LAUNCH();
+}
+
+// Frozen-BN backward, 3x3 pad 1, stride 1 or 2. dout/out [N][Ho][Wo][C], x
+// and dx [N][H][W][C] bf16; dx may be null (no input gradient wanted); out is
+// read under act 2 (ReLU6) only. part: [ddlw_depthwise_bwd_bn_nparts(N, H,
+// W)][9][C] fp32 scratch (the tiles lie over the input), dw: [C][9] fp32.
+DDLW_EXPORT int ddlw_depthwise_bwd_gated(const void* dout, const void* out,
+                                         const void* x, const void* w_t,
+                                         const void* scale, void* dx,
+                                         void* part, void* dw, int N, int H,
+                                         int W_, int C, int Ho, int Wo,
+                                         int stride, int act, void* stream) {
+  if (int e = dw_check("depthwise_bwd_gated", C, DW_K, DW_K, stride, 1, H, W_,
+                       Ho, Wo))
+    return e;
+  auto fail = [](const char* why) { return ddlw_fail("depthwise_bwd_gated", why); };
+  if (N <= 0) return fail("empty batch");
+  if (act != 0 && act != 2) return fail("act must be 0 (none) or 2 (ReLU6)");
+  if (!dout || !x || !scale || !part || !dw || (act == 2 && !out) || (dx && !w_t))
+    return fail("dout, x, scale, part, dw (out under ReLU6, w_t with dx) are required");
+  if ((long)N * H * W_ >= (1l << 30))
+    return fail("tensor too large for 32-bit pixel indexing");
+  const int nparts = ddlw_depthwise_bwd_bn_nparts(N, H, W_, nullptr);
+  dim3 grid((unsigned)cdiv(C >> 3, DWB_CV), nparts);
+  with_int<1, 2>(stride, [&](auto ST) {
+    with_int<0, 2>(act, [&](auto ACTc) {
+      with_bool(dx != nullptr, [&](auto DX) {
+        hipLaunchKernelGGL(
+            (k_depthwise_bwd_gated<decltype(ST)::value, decltype(ACTc)::value,
+                                   decltype(DX)::value>),
+            grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout,
+            (const bf16_t*)out, (const bf16_t*)x, (const bf16_t*)w_t,
+            (const float*)scale, (bf16_t*)dx, (float*)part, N, H, W_, C, Ho, Wo);
+      });
+    });
+  });
+  DDLW_CHECK_LAUNCH_OR_RETURN();
   hipLaunchKernelGGL(k_depthwise_wgrad_finalize,
                      dim3((C + 31) / 32, DW_K * DW_K), dim3(256), 0,
                      (hipStream_t)stream, (const float*)part, (float*)dw, C,

@@ -30,14 +30,7 @@
 //     MobileNetV2 K values with little waste), a block 4 waves = 128 rows.
 //     Consecutive blocks walk the N tiles of one row tile so the re-read of
 //     x comes from cache.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 pw_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float pw_f32x4;
-
-#define PW_MR 2                    // 16-row fragments per wave
-#define PW_WAVES 4
-#define PW_BM (PW_WAVES * PW_MR * 16)
+#include "pointwise.h"
 
 // The tile/MFMA body, shared AS TEXT by k_pw_conv and k_pw_conv_stats. (As an
 // inlined device function the same statements change the emitted code of the
@@ -231,17 +224,6 @@ __global__ __launch_bounds__(256) void k_pw_conv_stats(
     psum[mtile * K + k0 + t] = ts;
     psq[mtile * K + k0 + t] = tq;
   }
-}
-
-// 32-channel fragment pairs per wave: the smallest listed NP that covers K in
-// one tile, else whichever of 5 / 6 wastes fewer pairs over ceil(K/32).
-static int pw_pick_np(int K) {
-  const int kp = (K + 31) / 32;
-  if (kp <= 3) return kp;
-  if (kp <= 5) return 5;
-  if (kp == 6) return 6;
-  const int w5 = (kp + 4) / 5 * 5, w6 = (kp + 5) / 6 * 6;
-  return w5 < w6 ? 5 : 6;
 }
 
 // x [M][C], w [K][C], y/res [M][K] bf16; scale/bias fp32 [K] (both or

@@ -20,6 +20,9 @@ Under ``DDLW_DW_TRAIN=1`` the depthwise stage between them runs on
 ``_DwConvBnActFn`` the same way, its stride-1 backward in one kernel.
 A marked training stem fed a uint8 batch runs on ``_StemU8BnActFn`` the same
 way, its forward and its weight gradient reading the bytes.
+A trainable block under FROZEN BatchNorms (``fine_tune_bn="frozen"``) runs on
+``_PwConvFrozenBnActFn`` / ``_DwConvFrozenBnActFn``: folded forward kernels,
+gated backward kernels (``DDLW_FROZEN_BN``).
 """
 from __future__ import annotations
 
@@ -588,3 +591,242 @@ def inverted_residual_train_forward(block, x: torch.Tensor) -> torch.Tensor:
         else:
             h = bn(conv(h))
     return x + h if block.use_res else h
+
+
+# --------------------------------------------------------------------------- #
+# Fine-tuned block with FROZEN BatchNorm: folded forward, gated backward
+# --------------------------------------------------------------------------- #
+#
+# ``fine_tune_bn="frozen"`` (models/mobilenet_v2.py): the BatchNorms of the
+# trainable suffix stay in eval mode with no-grad gamma / beta (the
+# ``FrozenBatchNorm2d`` convention: a constant per-channel affine; NOT Keras's
+# trainable gamma / beta under ``training=False``), only the conv weights
+# train. A stage is then ``out = act(scale[k] * conv(x, W) + bias[k] (+ res))``
+# on the folded forward kernels, and its whole BN + ReLU6 backward is
+#   g16 = gate(out) ? bf16(fp32(dout) * scale[k]) : 0,  gate = 0 < out < 6,
+# formed inside the conv's backward kernels (hip/pointwise_frozen.hip,
+# k_depthwise_bwd_gated): no reductions, no dz tensor, no mask tensor.
+
+
+def _gated_grad(dout, out, scale, act: int) -> torch.Tensor:
+    """g16 as a tensor, for a direction ``binding.frozen_bn_route`` keeps on
+    the kernels the gated ones replace."""
+    g = (dout.float() * scale.view(1, -1, 1, 1)).to(torch.bfloat16)
+    if act == 2:
+        g = g * ((out > 0) & (out < 6))
+    return g.contiguous(memory_format=torch.channels_last)
+
+
+def _bf16_cl(dout: torch.Tensor) -> torch.Tensor:
+    dout = dout.contiguous(memory_format=torch.channels_last)
+    return dout if dout.dtype == torch.bfloat16 else dout.to(torch.bfloat16)
+
+
+class _ResJoin:
+    """The gradient that joins at a block's input through the residual: the
+    project stage's backward leaves the block's ``dout`` here and the expand
+    stage's dgrad adds it in its epilogue (``acc``), so the eager ``x + h``
+    backward add is gone. The expand stage's backward runs after the project
+    stage's: its gradient depends on it."""
+
+    def __init__(self):
+        self.dout = None
+
+
+class _PwConvFrozenBnActFn(torch.autograd.Function):
+    """conv1x1 -> frozen BatchNormAct2d (+ residual). Forward: the folded
+    pointwise kernel. Backward: the gated dgrad / wgrad kernels, each only
+    when needed. ``join`` is a ``_ResJoin``: a stage with ``res`` fills it
+    (``res`` itself gets no gradient from here), a stage without takes its
+    ``acc`` from it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, bias, act: int, res, join):
+        x = x.contiguous(memory_format=torch.channels_last)
+        out = binding.pw_conv_fwd(x, weight, scale, bias, act, res)
+        ctx.save_for_backward(x, weight, out, scale)
+        ctx.act, ctx.join, ctx.fills = act, join, res is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .conv import pw_conv_backward
+
+        x, weight, out, scale = ctx.saved_tensors
+        dout = _bf16_cl(dout)
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        acc = None
+        if ctx.join is not None:
+            if ctx.fills:
+                ctx.join.dout = dout
+            else:
+                acc, ctx.join.dout = ctx.join.dout, None
+        k, c = weight.shape[0], weight.shape[1]
+        rows = x.shape[0] * x.shape[2] * x.shape[3]
+        fast_dx = need_dx and binding.frozen_bn_route("pw_dgrad", c, k, 1, rows)
+        fast_dw = need_dw and binding.frozen_bn_route("pw_wgrad", c, k, 1, rows)
+        dx = dw = None
+        if fast_dx:
+            dx = binding.pw_dgrad_gated(dout, out, weight, scale, ctx.act, x.shape, acc)
+        if fast_dw:
+            dw = binding.pw_wgrad_gated(dout, out, x, scale, ctx.act,
+                                        weight.shape).to(weight.dtype)
+        if (need_dx and not fast_dx) or (need_dw and not fast_dw):
+            g = _gated_grad(dout, out, scale, ctx.act)
+            gx, gw = pw_conv_backward(g, x, weight, need_dx and not fast_dx,
+                                      need_dw and not fast_dw)
+            if gx is not None:
+                dx = gx if acc is None else gx + acc
+            if gw is not None:
+                dw = gw
+        return dx, dw, None, None, None, None, None
+
+
+class _DwConvFrozenBnActFn(torch.autograd.Function):
+    """depthwise conv3x3 (pad 1, stride 1 or 2) -> frozen BatchNormAct2d.
+    Forward: the folded depthwise kernel. Backward: one gated kernel for dx
+    and dW."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, bias, act: int, stride: int):
+        x = x.contiguous(memory_format=torch.channels_last)
+        out = binding.depthwise_fwd_ep(x, weight, scale, bias, act, stride, 1)
+        ctx.save_for_backward(x, weight, out, scale)
+        ctx.act, ctx.stride = act, stride
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, out, scale = ctx.saved_tensors
+        dout = _bf16_cl(dout)
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        c = weight.shape[0]
+        rows = out.shape[0] * out.shape[2] * out.shape[3]
+        dx = dw = None
+        if binding.frozen_bn_route("dw_bwd", c, c, ctx.stride, rows):
+            dx, dw = binding.depthwise_bwd_gated(dout, out, x, weight, scale,
+                                                 ctx.act, ctx.stride, need_dx)
+        else:
+            g = _gated_grad(dout, out, scale, ctx.act)
+            if need_dx:
+                dx = binding.depthwise_dgrad(g, weight, x.shape, ctx.stride, 1)
+            if need_dw:
+                dw = binding.depthwise_wgrad(g, x, weight.shape, ctx.stride, 1)
+        if dw is not None:
+            dw = dw.to(weight.dtype) if need_dw else None
+        return dx, dw, None, None, None, None
+
+
+def _bn_frozen(bn) -> bool:
+    return (not bn.training and _bn_fp32(bn)
+            and not bn.weight.requires_grad and not bn.bias.requires_grad)
+
+
+def _frozen_bn_env(x: torch.Tensor) -> bool:
+    if not torch.is_grad_enabled():
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16):
+        return False
+    if os.environ.get("DDLW_DISABLE_HIP_OPS", "0") == "1":
+        return False
+    if os.environ.get("DDLW_CONV", "auto") == "stock":
+        return False
+    return os.environ.get("DDLW_FROZEN_BN", "")[:1] != "0"
+
+
+def _frozen_stage_kind(conv, bn):
+    """``"pw"`` / ``"dw"`` for a stage the frozen-BN Functions take."""
+    if conv.weight.dtype != torch.bfloat16 or _ACT[bn.act] not in (0, 2):
+        return None
+    if _is_pointwise(conv) and binding.pw_gated_supported(conv.in_channels,
+                                                          conv.out_channels):
+        return "pw"
+    if _is_depthwise3x3(conv):
+        return "dw"
+    return None
+
+
+def _frozen_stage_routed(kind, conv, rows_in: int, rows_out: int) -> bool:
+    """Does any direction of the stage run on a gated kernel?"""
+    c, k = conv.in_channels, conv.out_channels
+    if kind == "pw":
+        return (binding.frozen_bn_route("pw_dgrad", c, k, 1, rows_in)
+                or binding.frozen_bn_route("pw_wgrad", c, k, 1, rows_in))
+    return binding.frozen_bn_route("dw_bwd", c, c, conv.stride[0], rows_out)
+
+
+def conv_bn_frozen_fusable(conv, bn, x: torch.Tensor) -> bool:
+    """One conv + BatchNormAct2d stage (the 320 -> 1280 tail) on the frozen-BN
+    stage Function: the conditions of ``inverted_residual_frozen_bn_fusable``
+    for a single stage."""
+    if not (_frozen_bn_env(x) and _bn_frozen(bn)):
+        return False
+    kind = _frozen_stage_kind(conv, bn)
+    if kind is None:
+        return False
+    rows = x.shape[0] * x.shape[2] * x.shape[3]
+    s = conv.stride[0]
+    rows_out = x.shape[0] * ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)
+    return _frozen_stage_routed(kind, conv, rows, rows_out)
+
+
+def conv_bn_frozen(conv, bn, x: torch.Tensor, res=None, join=None) -> torch.Tensor:
+    """One stage on its frozen-BN Function (the caller checked
+    ``_frozen_stage_kind``)."""
+    scale, bias = bn.folded_scale_bias()
+    act = _ACT[bn.act]
+    if _is_pointwise(conv):
+        return _PwConvFrozenBnActFn.apply(x, conv.weight, scale, bias, act, res, join)
+    return _DwConvFrozenBnActFn.apply(x, conv.weight, scale, bias, act, conv.stride[0])
+
+
+def inverted_residual_frozen_bn_fusable(block, x: torch.Tensor) -> bool:
+    """The conditions under which a block of the trainable suffix takes the
+    frozen-BN stage Functions: grad enabled, every BN of the block in eval
+    mode with fp32 buffers and no-grad parameters, bf16 conv weights of the
+    pointwise / depthwise 3x3 shapes the gated kernels take, CUDA bf16 input,
+    neither ``DDLW_DISABLE_HIP_OPS=1`` nor ``DDLW_CONV=stock``, and
+    ``DDLW_FROZEN_BN`` (``0`` never, ``1`` always, unset: some direction of
+    some stage is a measured winner, ``binding.frozen_bn_route``). All read
+    at call time."""
+    if not _frozen_bn_env(x) or x.dim() != 4:
+        return False
+    stages = _stages(block)
+    if not all(_bn_frozen(bn) for _, bn in stages):
+        return False
+    kinds = [_frozen_stage_kind(conv, bn) for conv, bn in stages]
+    if any(k is None for k in kinds):
+        return False
+    n, _, h, w = x.shape
+    routed = False
+    for kind, (conv, _) in zip(kinds, stages):
+        s = conv.stride[0]
+        ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+        routed = routed or _frozen_stage_routed(kind, conv, n * h * w, n * ho * wo)
+        h, w = ho, wo
+    return routed
+
+
+def inverted_residual_frozen_bn_forward(block, x: torch.Tensor) -> torch.Tensor:
+    """Every stage on its frozen-BN Function. The residual rides the project
+    stage's forward epilogue, and its gradient (the block's ``dout``) rides
+    the expand stage's dgrad epilogue as ``acc`` (``_ResJoin``) when the
+    input wants a gradient at all; a residual block whose first stage is not
+    pointwise keeps the eager add."""
+    stages = _stages(block)
+    x = x.contiguous(memory_format=torch.channels_last)
+    fused_res = (block.use_res and _is_pointwise(stages[-1][0])
+                 and (not x.requires_grad
+                      or (len(stages) == 3 and _is_pointwise(stages[0][0]))))
+    join = _ResJoin() if (fused_res and x.requires_grad) else None
+    h = x
+    for i, (conv, bn) in enumerate(stages):
+        last = i == len(stages) - 1
+        if _is_pointwise(conv):
+            h = conv_bn_frozen(conv, bn, h, res=x.detach() if (fused_res and last) else None,
+                               join=join if (i == 0 or last) else None)
+        else:
+            h = conv_bn_frozen(conv, bn, h)
+    if block.use_res and not fused_res:
+        return x + h
+    return h
